@@ -25,12 +25,26 @@ onto rank 0, inside the timed region, assembles the image
 wall time. --shard samples keeps the weak-scaling alternative (every rank the
 whole image, disjoint sample indices).
 
-Rank 0 at N=1 also times the CPU oracle (oracle/, a C restatement of the
+A plain run does what the headline figure needs and no more: set up, warm up,
+time the --steps steps, write --dump-outputs, print the line (value,
+ms_per_step, the workload and the device counters' per-sample figures).
+
+--dump-outputs DIR: after the timed steps rank 0 writes DIR/accum.npy, what a
+caller of the timed path holds after its last step: the assembled float32
+accumulator (H, W, 3), the sum of every timed sample per pixel. Above 60 MB
+(C5) it is a fixed sample of the pixels instead, (n, 3) in ascending pixel
+order (dump_pixels: seeded, so two builds sample the same pixels). Scene,
+camera, seed and sample indices depend on the arguments alone, so two runs
+with the same arguments render the same samples.
+
+--full adds everything else, as the benchmark ran before the option existed.
+Rank 0 at N=1 times the CPU oracle (oracle/, a C restatement of the
 reference's kernels.py: the reference's ti.cpu path cannot run here, Taichi is
-absent) on a bounded slice of the same workload, and reports the dominant
-kernel's roofline from HIP events recorded around its launches in the timed
-region: per-launch time = the union of the launches' [start, end] intervals
-divided by the launch count, because consecutive megakernel calls are
+absent) on a bounded slice of the same workload (--no-cpu-baseline leaves it
+out), and the line carries the dominant kernel's roofline from HIP events
+recorded around its launches (the megakernel's in the timed region, the
+wavefront's in a second pass over the same steps): per-launch time = the
+union of the launches' [start, end] intervals divided by the launch count, because consecutive megakernel calls are
 pipelined on two streams and overlap (tools/trace_busy.py computes the same
 figure from a rocprofv3 kernel trace). `roofline.traffic` (PMC HBM-side bytes per launch, profiles/traffic.json)
 and `valu_diagnostic` (VALU issue share, lane efficiency and wave wait share of
@@ -108,8 +122,15 @@ def parse(argv=None):
     p.add_argument('--width', type=int, default=None)
     p.add_argument('--max-depth', type=int, default=50)
     p.add_argument('--seed', type=int, default=0)
-    p.add_argument('--cpu-seconds', type=float, default=12.0)
-    p.add_argument('--no-cpu-baseline', action='store_true')
+    p.add_argument('--full', action='store_true',
+                   help='also what the headline figure does not need: per-kernel HIP-event timing and the '
+                        "dominant kernel's roofline (the wavefront's in a second pass over the steps), the "
+                        'committed PMC figures, and at --gpus 1 the CPU oracle baseline')
+    p.add_argument('--dump-outputs', default='', metavar='DIR',
+                   help='rank 0 writes DIR/accum.npy after the timed steps: the assembled float32 accumulator '
+                        '(H, W, 3), or above 60 MB a fixed seeded sample of its pixels (n, 3)')
+    p.add_argument('--cpu-seconds', type=float, default=12.0, help='--full: time budget of the CPU baseline')
+    p.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline')
     p.add_argument('--save-image', default='')
     p.add_argument('--save-accum', default='',
                    help='rank 0 writes the assembled float32 accumulator (H, W, 3) to this .npy file')
@@ -250,6 +271,32 @@ def measured_traffic(a, kernel):
     return {'bytes_per_launch': r['bytes_per_launch'], 'source': r['source']}
 
 
+DUMP_LIMIT_BYTES = 60_000_000  # --dump-outputs keeps its files within 64 MB, .npy headers included
+DUMP_SAMPLE_SEED = 20240  # of the pixel sample a larger accumulator is cut down to
+
+
+def dump_pixels(H, W, limit=DUMP_LIMIT_BYTES):
+    """Flat pixel indices (ascending) --dump-outputs keeps of an H x W x 3
+    float32 accumulator: None = every pixel when it fits `limit` bytes, else a
+    fixed sample (seeded, a function of H, W and limit alone) that does."""
+    import numpy as np
+    n = limit // 12
+    if H * W <= n:
+        return None
+    return np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(H * W, size=n, replace=False))
+
+
+def dump_outputs(directory, acc):
+    """Write DIR/accum.npy from the (H, W, 3) float32 accumulator tensor."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    a = acc.cpu().numpy()
+    idx = dump_pixels(a.shape[0], a.shape[1])
+    if idx is not None:
+        a = a.reshape(-1, 3)[idx]
+    np.save(os.path.join(directory, 'accum.npy'), np.ascontiguousarray(a, dtype=np.float32))
+
+
 class BenchRun:
     """The hot-path call shape of one bench rank: workload, device scene,
     frame (this rank's bands), and one step = one render call of
@@ -302,6 +349,59 @@ def describe(a, W, H, world, shard):
                         if world > 1 else 'single GPU'),
     }
     return total_spp, ('weak' if a.shard == 'samples' else 'strong'), cfg
+
+
+def full_report(a, kt, inline, segments, tail, samples_rank, pixels_rank, b_sample, world):
+    """--full: the line's per-kernel entries (roofline, valu_diagnostic,
+    kernels_ms, kernels_busy_ms) from the KernelTimer `kt` that recorded the
+    steps' launches (`inline`: in the timed region) and the device counters."""
+    prof = kt.result
+    # per-launch GPU time = union of the kind's launch intervals / launches
+    # (ptmi_prof_stop_busy): pipelined megakernel calls overlap their
+    # neighbours, so each launch's own start->end spans about two steps
+    dom = max((k for k in prof if prof[k]['launches']), key=lambda k: prof[k]['busy_ms'])
+    unit_name, unit_bytes = ALGO_BYTES[dom]
+    if unit_bytes is None:
+        unit_bytes = b_sample
+    units = kernel_units(dom, segments, tail, samples_rank, pixels_rank, prof)
+    dom_ms = prof[dom]['busy_ms']
+    launches = prof[dom]['launches']
+    avg_launch_ms = dom_ms / max(1, launches)
+    achieved = units * unit_bytes / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
+    # the committed PMC passes were collected on the full frame at one GPU
+    traffic = measured_traffic(a, dom) if world == 1 or a.shard == 'samples' else None
+    valu = valu_diagnostic(a, dom)
+    return {
+        'roofline': {
+            'bound': 'hbm', 'kernel': dom,
+            'achieved': round(achieved, 3), 'peak': HBM_PEAK_GBPS, 'unit': 'GB/s',
+            'frac': round(achieved / HBM_PEAK_GBPS, 6),
+            'traffic': traffic['bytes_per_launch'] if traffic else None,
+            'traffic_source': traffic['source'] if traffic else None,
+            # what the counters say the kernel really moves to/from HBM (incl.
+            # Infinity-Cache hits): PMC bytes per launch / busy time per launch
+            'measured_GBps': round(traffic['bytes_per_launch'] / (avg_launch_ms * 1e-3) / 1e9, 3)
+            if traffic and avg_launch_ms > 0 else None,
+            # compute side of the same kernel: VALU issue share x lane efficiency
+            # (profiles/valu.json): the fraction of the chip's FP32 lanes doing work
+            'compute_frac': round(valu['valu_issue_frac'] * valu['lane_efficiency'], 4) if valu else None,
+            'achieved_note': ('achieved = algorithmic bytes (SURVEY.md §8d B_sample model) / busy time; '
+                              'it is not HBM traffic: see measured_GBps'),
+            'algorithmic_bytes_per_launch': round(units * unit_bytes / max(1, launches), 1),
+            'unit_of_work': f'{unit_bytes:.1f} B per {unit_name[:-1] if unit_name.endswith("s") else unit_name}',
+            'avg_launch_ms': round(avg_launch_ms, 5),
+            'avg_launch_own_ms': round(prof[dom]['ms'] / max(1, launches), 5),
+            'launches': launches,
+            'timing_truncated': bool(kt.truncated),
+            'timing': ('HIP events per launch on its stream, ' +
+                       ('in the timed region' if inline else 'in a second pass over the same steps') +
+                       "; avg_launch_ms = union of the launches' [start, end] intervals / launches "
+                       '(pipelined launches overlap; avg_launch_own_ms = mean start->end of one launch)'),
+        },
+        'valu_diagnostic': valu,
+        'kernels_ms': {k: round(v['ms'], 3) for k, v in prof.items() if v['launches']},
+        'kernels_busy_ms': {k: round(v['busy_ms'], 3) for k, v in prof.items() if v['launches']},
+    }
 
 
 def throughput(samples_all, elapsed_max_s):
@@ -377,13 +477,13 @@ def main():
     if pg:
         dist.barrier()
 
-    # Per-kernel durations (roofline): HIP events around every launch, on the
+    # --full only. Per-kernel durations (roofline): HIP events around every launch, on the
     # stream it runs on. The megakernel (2 events per 18-ms launch) is timed
     # inside the timed region. The wavefront's pipes are concurrent streams and
     # an event per launch costs them ~10 %, so its kernels are timed in a
     # second pass over the same K steps into a scratch accumulator and the
-    # timed region runs without events.
-    inline = a.variant == 'mk'
+    # timed region runs without events. A plain run records no events at all.
+    inline = a.full and a.variant == 'mk'
     with _lib.KernelTimer(max_launches=100_000 if inline else 0) as kt:
         torch.cuda.synchronize(dev)
         if pg:
@@ -403,7 +503,7 @@ def main():
     render_rank = (t_render_end - t0) if t_render_end is not None else elapsed_rank
     elapsed = max_over_ranks(elapsed_rank, dev if a.dist_backend == 'nccl' else None)
     cnt = integ.read_counters()
-    if not inline:
+    if a.full and not inline:
         acc_k = torch.zeros_like(acc)
         with _lib.KernelTimer(max_launches=100_000) as kt:
             for k in range(a.steps):
@@ -416,28 +516,15 @@ def main():
     value = throughput(samples_all, elapsed)
     total_spp, scaling, config = describe(a, W, H, world, shard)
 
-    prof = kt.result
-    # per-launch GPU time = union of the kind's launch intervals / launches
-    # (ptmi_prof_stop_busy): pipelined megakernel calls overlap their
-    # neighbours, so each launch's own start->end spans about two steps
-    dom = max((k for k in prof if prof[k]['launches']), key=lambda k: prof[k]['busy_ms'])
     S = cnt['segments'] / samples_rank
     M = cnt['medium'] / samples_rank
     b_sample = 44 + 24 + 128 * S  # SURVEY.md §8d whole-pipeline algorithmic bytes per sample
-    unit_name, unit_bytes = ALGO_BYTES[dom]
-    if unit_bytes is None:
-        unit_bytes = b_sample
     # segments traced by the wavefront's tail launch (wf_drain) belong to its
     # time, not to wf_intersect's / wf_scatter's
     tail = (integ.tail_segments() or 0) if a.variant == 'wf' else 0
-    units = kernel_units(dom, cnt['segments'], tail, samples_rank, W * rows_rank, prof)
-    dom_ms = prof[dom]['busy_ms']
-    launches = prof[dom]['launches']
-    avg_launch_ms = dom_ms / max(1, launches)
-    achieved = units * unit_bytes / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
-    # the committed PMC passes were collected on the full frame at one GPU
-    traffic = measured_traffic(a, dom) if world == 1 or a.shard == 'samples' else None
-    valu = valu_diagnostic(a, dom)
+    extra = full_report(a, kt, inline, cnt['segments'], tail, samples_rank, W * rows_rank, b_sample,
+                        world) if a.full else {}
+    dom_ms = extra['kernels_busy_ms'][extra['roofline']['kernel']] if a.full else 0.0
     per_rank = gather_ranks([rank, rows_rank, samples_rank, render_rank, elapsed_rank, dom_ms],
                             dev if a.dist_backend == 'nccl' else 'cpu', world)
 
@@ -454,37 +541,10 @@ def main():
         'scaling': scaling,
         'vs_baseline': None,
         'dtype': 'f32',
+        'full': bool(a.full),
         'data': data_note,
         'config': config,
-        'roofline': {
-            'bound': 'hbm', 'kernel': dom,
-            'achieved': round(achieved, 3), 'peak': HBM_PEAK_GBPS, 'unit': 'GB/s',
-            'frac': round(achieved / HBM_PEAK_GBPS, 6),
-            'traffic': traffic['bytes_per_launch'] if traffic else None,
-            'traffic_source': traffic['source'] if traffic else None,
-            # what the counters say the kernel really moves to/from HBM (incl.
-            # Infinity-Cache hits): PMC bytes per launch / busy time per launch
-            'measured_GBps': round(traffic['bytes_per_launch'] / (avg_launch_ms * 1e-3) / 1e9, 3)
-            if traffic and avg_launch_ms > 0 else None,
-            # compute side of the same kernel: VALU issue share x lane efficiency
-            # (profiles/valu.json): the fraction of the chip's FP32 lanes doing work
-            'compute_frac': round(valu['valu_issue_frac'] * valu['lane_efficiency'], 4) if valu else None,
-            'achieved_note': ('achieved = algorithmic bytes (SURVEY.md §8d B_sample model) / busy time; '
-                              'it is not HBM traffic: see measured_GBps'),
-            'algorithmic_bytes_per_launch': round(units * unit_bytes / max(1, launches), 1),
-            'unit_of_work': f'{unit_bytes:.1f} B per {unit_name[:-1] if unit_name.endswith("s") else unit_name}',
-            'avg_launch_ms': round(avg_launch_ms, 5),
-            'avg_launch_own_ms': round(prof[dom]['ms'] / max(1, launches), 5),
-            'launches': launches,
-            'timing_truncated': bool(kt.truncated),
-            'timing': ('HIP events per launch on its stream, ' +
-                       ('in the timed region' if inline else 'in a second pass over the same steps') +
-                       "; avg_launch_ms = union of the launches' [start, end] intervals / launches "
-                       '(pipelined launches overlap; avg_launch_own_ms = mean start->end of one launch)'),
-        },
-        'valu_diagnostic': valu,
-        'kernels_ms': {k: round(v['ms'], 3) for k, v in prof.items() if v['launches']},
-        'kernels_busy_ms': {k: round(v['busy_ms'], 3) for k, v in prof.items() if v['launches']},
+        **extra,
         'segments_per_sample': round(S, 4),
         'tail_segments_per_sample': round(tail / samples_rank, 4) if a.variant == 'wf' else None,
         'collectives': ({'backend': dist.get_backend(), 'world_size': world_size,
@@ -493,11 +553,14 @@ def main():
         'medium_traversals_per_sample': round(M, 4),
         'pipeline_algorithmic_GBps': round(value * 1e6 * b_sample / 1e9, 3),
         'ranks': [{'rank': int(r[0]), 'rows': int(r[1]), 'samples': int(r[2]), 'render_s': round(r[3], 4),
-                   'elapsed_s': round(r[4], 4), 'kernel_busy_ms': round(r[5], 3)} for r in per_rank],
+                   'elapsed_s': round(r[4], 4), 'kernel_busy_ms': round(r[5], 3) if a.full else None}
+                  for r in per_rank],
     }
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, acc)
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         out['cpu_baseline'] = cpu_baseline(sa, cam, bg, a.scene, a.variant, a.max_depth, a.seed, a.cpu_seconds)
-    elif rank == 0:
+    elif a.full and rank == 0:
         out['cpu_baseline'] = None
     if rank == 0:
         if a.save_accum:

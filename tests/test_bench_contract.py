@@ -130,3 +130,33 @@ def test_wavefront_tail_segments_are_the_drains_units():
     # every kernel the roofline can name has a unit
     for k in bench.ALGO_BYTES:
         bench.kernel_units(k, seg, tail, samples, pix, prof)
+
+def test_plain_run_is_the_default_and_full_is_an_option():
+    a = _args(['--gpus', '1', '--steps', '3', '--warmup', '1'])
+    assert a.full is False and a.dump_outputs == '' and a.steps == 3 and a.warmup == 1
+    a = _args(['--full', '--dump-outputs', 'out', '--no-cpu-baseline'])
+    assert a.full is True and a.dump_outputs == 'out' and a.no_cpu_baseline is True
+
+
+def test_dump_keeps_every_pixel_up_to_the_limit_and_a_fixed_sample_above():
+    """--dump-outputs: C2's accumulator (7.7 MB) whole; C5's (99.5 MB) cut to
+    a sample within 60 MB (the file under 64 MB) that is the same on every call."""
+    import numpy as np
+    assert bench.dump_pixels(800, 800) is None
+    idx = bench.dump_pixels(2160, 3840)
+    assert bench.DUMP_LIMIT_BYTES + 4096 <= 64_000_000  # room for the .npy header
+    assert bench.DUMP_LIMIT_BYTES - 12 < idx.size * 12 <= bench.DUMP_LIMIT_BYTES
+    assert (np.diff(idx) > 0).all() and idx[0] >= 0 and idx[-1] < 2160 * 3840
+    assert np.array_equal(idx, bench.dump_pixels(2160, 3840))
+    small = bench.dump_pixels(5, 7, limit=120)  # 10 of 35 pixels
+    assert small.size == 10 and len(set(small.tolist())) == 10
+
+
+def test_dump_outputs_writes_float32_accum(tmp_path):
+    import numpy as np
+    import torch
+    acc = torch.arange(5 * 7 * 3, dtype=torch.float32).reshape(5, 7, 3)
+    bench.dump_outputs(str(tmp_path / 'd'), acc)
+    got = np.load(tmp_path / 'd' / 'accum.npy')
+    assert got.dtype == np.float32 and np.array_equal(got, acc.numpy())
+    assert sorted(os.listdir(tmp_path / 'd')) == ['accum.npy']

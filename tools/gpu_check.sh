@@ -3,7 +3,7 @@
 # Steps (default: tests smoke c2 c3):
 #   tests        full `pytest -m gpu` suite
 #   smoke        __graft_entry__.smoke()
-#   c2|c3|c4|c5  bench.py --preset <c> (one JSON line)
+#   c2|c3|c4|c5  bench.py --preset <c> --full (one JSON line with the roofline and the CPU baseline)
 #   trace_<c>    rocprofv3 --kernel-trace --stats of the bench command
 #   fetch_<c> / write_<c>   FETCH_SIZE / WRITE_SIZE PMC passes (4 steps)
 #   dist2        2-rank gloo rehearsal of the multi-GPU bench on the one GPU
@@ -50,7 +50,7 @@ for s in $STEPS; do
   case $s in
     tests) step tests 900 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread ;;
     smoke) step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    c2|c3|c4|c5) step bench_$s 300 python bench.py --preset $s ;;
+    c2|c3|c4|c5) step bench_$s 300 python bench.py --preset $s --full ;;
     trace_*) c=${s#trace_}; step $s 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/rocprof" -o $c -- python bench.py --preset $c --no-cpu-baseline ;;
     fetch_*) c=${s#fetch_}; step $s 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc" -o fetch_$c -- python bench.py --preset $c --steps 4 --no-cpu-baseline ;;
     write_*) c=${s#write_}; step $s 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc" -o write_$c -- python bench.py --preset $c --steps 4 --no-cpu-baseline ;;
