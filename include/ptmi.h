@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define PTMI_ABI_VERSION 7
+#define PTMI_ABI_VERSION 8
 #define PTMI_MAX_IMAGES 16
 
 enum {
@@ -249,6 +249,80 @@ int ptmi_clear(const ptmi_frame *frame, float *accum, void *stream);
  * u8 = clip(sqrt(max(0, accum * (1/max(1,spp)))) * 255.999, 0, 255). */
 int ptmi_tonemap(const float *accum, uint8_t *out, int32_t width, int32_t height, int32_t spp,
                  void *stream);
+
+/* ---- Per-pixel error estimates and adaptive tile sampling (ABI v8). The
+ * reference has no counterpart: TaichiRenderer always renders
+ * cam.samples_per_pixel samples of every pixel (renderer.py:405-409).
+ *
+ * stats: a second per-pixel buffer, height x width x 4 f32, row-major like
+ * accum, 16-byte aligned: {n, mean, M2, 0} of the sample luminance
+ * y = (0.2126f*r + 0.7152f*g) + 0.0722f*b, updated per sample in sample order
+ * (Welford): n1 = n + 1; d = y - mean; mean1 = mean + d / n1;
+ * M2 = M2 + d * (y - mean1). [3] is reserved (cleared, never written).
+ * Pixel error: e = +inf for n < 2, else
+ * sqrtf((M2 / (n - 1)) / n) / (fabsf(mean) + 0.01f). All f32, one rounding
+ * per operation, so numpy f32 reproduces every value bit for bit.
+ *
+ * Tiles are the staged megakernel's 64-pixel tiles of the frame's local rows
+ * (8x8; on banded frames 16x4, 32x2 or 64x1, as tall as the band allows),
+ * numbered t = ty * tiles_x + tx; lane p of a tile is pixel
+ * (p & (tile_w - 1), p >> log2 tile_w) of it. ptmi_mk_tile_grid gives the
+ * tile size and the grid (host only). */
+int ptmi_mk_tile_grid(const ptmi_frame *frame, int32_t *tile_w, int32_t *tile_h, int32_t *tiles_x,
+                      int32_t *tiles_y);
+
+/* ptmi_clear for the stats buffer: zeroes the frame's pixel set. */
+int ptmi_stats_clear(const ptmi_frame *frame, float *stats, void *stream);
+
+/* ptmi_mk_trace_ws restricted to the tiles tile_list[0 .. n_tiles) (device
+ * int32 ids, ascending order keeps the work shards spatially interleaved):
+ * only their pixels are traced and written to the staging slots, which keep
+ * the [sample][frame pixel] layout, so workspace size and
+ * ptmi_mk_max_batch are those of ptmi_mk_trace_ws. Ids outside the grid are
+ * ignored on the device; n_tiles == 0 is a no-op; n_tiles above the grid's
+ * tile count is PTMI_EINVAL. Accepts sample_count == 1. Timed as kind 0. */
+int ptmi_mk_trace_tiles_ws(const ptmi_scene_view *scene, const ptmi_frame *frame, void *workspace,
+                           size_t workspace_bytes, const int32_t *tile_list, int32_t n_tiles,
+                           int32_t sample_begin, int32_t sample_count, uint64_t *counters, void *stream);
+
+/* ptmi_mk_resolve_ws plus the stats update: adds the sample_count staged
+ * colours of each pixel into accum in sample order (bit for bit what
+ * ptmi_mk_resolve_ws adds) and updates stats with each sample's luminance.
+ * tile_list == NULL: every pixel of the frame; otherwise the pixels of the
+ * listed tiles only: pixels of other tiles are neither read from staging nor
+ * written. Timed as kind 6 (mk_resolve). */
+int ptmi_mk_resolve_stats_ws(const ptmi_frame *frame, const void *workspace, size_t workspace_bytes,
+                             float *accum, float *stats, const int32_t *tile_list, int32_t n_tiles,
+                             int32_t sample_count, void *stream);
+
+/* ptmi_wf_render resolving every batch through the stats resolve (timed as
+ * kind 5, wf_resolve). The wavefront has no tile list: every call renders the
+ * whole frame. */
+int ptmi_wf_render_stats(const ptmi_scene_view *scene, const ptmi_frame *frame, void *workspace,
+                         size_t workspace_bytes, float *accum, float *stats, int32_t sample_begin,
+                         int32_t sample_count, uint64_t *counters, void *stream);
+
+/* Tile errors and states from stats. One wave per tile: lanes outside the
+ * frame contribute 0, the 64 lane values are summed by the xor butterfly
+ * (offsets 32, 16, 8, 4, 2, 1: v = v + v[lane ^ off]) and
+ * E = sum / (float)valid_lanes goes to tile_err[t]. tile_state[t] (int32: 1
+ * active, 0 done; the caller initialises it to 1) is updated monotonely:
+ *   active' = active && n_tile < max_spp && (n_tile < min_spp || E > threshold)
+ * with n_tile the n of the tile's lane 0 (all pixels of a tile share n). The
+ * comparison is false for E = NaN, so a NaN sample ends its tile instead of
+ * keeping it alive for ever. Then the active tiles' ids go to tile_list in
+ * ascending order and their count to *n_active (device int32). tile_state,
+ * tile_err and tile_list hold tiles_x * tiles_y entries. threshold < 0 (or
+ * NaN), min_spp < 0 and max_spp < min_spp are PTMI_EINVAL. Not timed. */
+int ptmi_tile_update(const ptmi_frame *frame, const float *stats, float threshold, int32_t min_spp,
+                     int32_t max_spp, int32_t *tile_state, float *tile_err, int32_t *tile_list,
+                     int32_t *n_active, void *stream);
+
+/* ptmi_tonemap with each pixel's own sample count n = stats[pixel][0]:
+ * scale = (float)(1.0 / (double)max(n, 1)). With one n for the whole image
+ * the result equals ptmi_tonemap(.., spp = n) bit for bit. */
+int ptmi_tonemap_stats(const float *accum, const float *stats, uint8_t *out, int32_t width, int32_t height,
+                       void *stream);
 
 /* Host-side binned-SAH BVH build (sah_bvh_builder.py:167-418 via
  * build_sah_bvh_from_primitives :445-485), f32 arithmetic identical to the

@@ -43,6 +43,34 @@ __global__ __launch_bounds__(kBlock) void tonemap_kernel(const float* __restrict
     out[i] = (uint8_t)(int32_t)v;
   }
 }
+
+// clear_kernel for the stats buffer: {n, mean, M2, reserved} = 0 on the frame's pixel set.
+__global__ __launch_bounds__(kBlock) void stats_clear_kernel(DevFrame fr, float4* __restrict__ stats) {
+  const int32_t npix = fr.w * fr.n_rows;
+  for (int32_t i = (int32_t)(blockIdx.x * kBlock + threadIdx.x); i < npix; i += (int32_t)(gridDim.x * kBlock)) {
+    int32_t lr = i / fr.w;
+    int32_t px = fr.x0 + (i - lr * fr.w);
+    int32_t py = frame_row(fr, lr);
+    stats[(size_t)py * (size_t)fr.width + (size_t)px] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  }
+}
+
+// tonemap_kernel with the scale of each pixel's own sample count n =
+// stats[pixel][0]: scale = (float)(1.0 / (double)max(n, 1)). With one n for
+// the whole image this is tonemap_kernel bit for bit.
+__global__ __launch_bounds__(kBlock) void tonemap_stats_kernel(const float* __restrict__ accum,
+                                                               const float4* __restrict__ stats,
+                                                               uint8_t* __restrict__ out, int32_t n) {
+  for (int32_t i = (int32_t)(blockIdx.x * kBlock + threadIdx.x); i < n; i += (int32_t)(gridDim.x * kBlock)) {
+    const float cnt = stats[i / 3].x;
+    const float scale = (float)(1.0 / (double)(cnt > 1.0f ? cnt : 1.0f));
+    float x = accum[i] * scale;
+    float g = sqrtf(pt_maxf(x, 0.0f));
+    float v = g * 255.999f;
+    v = v < 0.0f ? 0.0f : (v > 255.0f ? 255.0f : v);
+    out[i] = (uint8_t)(int32_t)v;
+  }
+}
 }  // namespace ptmi
 
 using namespace ptmi;
@@ -343,6 +371,132 @@ int ptmi_tonemap(const float* accum, uint8_t* out, int32_t width, int32_t height
   if (g > 4096) g = 4096;
   hipLaunchKernelGGL(tonemap_kernel, dim3(g), dim3(kBlock), 0, (hipStream_t)stream, accum, out, (int32_t)n, scale);
   return check_hip(hipGetLastError(), "tonemap launch");
+}
+
+// ------------------------------------------------------------- adaptive (ABI v8)
+static bool aligned4(const void* p) { return ((uintptr_t)p & 3u) == 0; }
+
+int ptmi_mk_tile_grid(const ptmi_frame* frame, int32_t* tile_w, int32_t* tile_h, int32_t* tiles_x, int32_t* tiles_y) {
+  DevFrame fr;
+  int rc = to_dev_frame(frame, fr);
+  if (rc) return rc;
+  if (!tile_w || !tile_h || !tiles_x || !tiles_y) return fail(PTMI_EINVAL, "tile grid output is NULL");
+  mk_tile_grid(fr, tile_w, tile_h, tiles_x, tiles_y);
+  return PTMI_OK;
+}
+
+int ptmi_stats_clear(const ptmi_frame* frame, float* stats, void* stream) {
+  DevFrame fr;
+  int rc = to_dev_frame(frame, fr);
+  if (rc) return rc;
+  if (!stats || !aligned16(stats)) return fail(PTMI_EINVAL, "stats NULL/misaligned");
+  int32_t npix = fr.w * fr.n_rows;
+  if (npix == 0) return PTMI_OK;
+  unsigned g = (unsigned)((npix + kBlock - 1) / kBlock);
+  if (g > 4096) g = 4096;
+  hipLaunchKernelGGL(stats_clear_kernel, dim3(g), dim3(kBlock), 0, (hipStream_t)stream, fr, (float4*)stats);
+  return check_hip(hipGetLastError(), "stats clear launch");
+}
+
+int ptmi_mk_trace_tiles_ws(const ptmi_scene_view* scene, const ptmi_frame* frame, void* workspace,
+                           size_t workspace_bytes, const int32_t* tile_list, int32_t n_tiles, int32_t sample_begin,
+                           int32_t sample_count, uint64_t* counters, void* stream) {
+  DevScene sc;
+  DevFrame fr;
+  int rc = to_dev_scene(scene, sc);
+  if (rc) return rc;
+  if ((rc = to_dev_frame(frame, fr))) return rc;
+  if ((rc = check_traversal(sc, fr))) return rc;
+  if (sample_begin < 0 || sample_count < 1) return fail(PTMI_EINVAL, "bad sample range");
+  if (n_tiles < 0 || (int64_t)n_tiles > mk_tile_count(fr))
+    return fail(PTMI_EINVAL, "n_tiles %d outside [0, %lld]", n_tiles, (long long)mk_tile_count(fr));
+  if (n_tiles > 0 && (!tile_list || !aligned4(tile_list))) return fail(PTMI_EINVAL, "tile_list NULL/misaligned");
+  const int32_t npix = fr.w * fr.n_rows;
+  if (npix == 0) return PTMI_OK;
+  if ((int64_t)sample_count > mk_max_batch(fr))
+    return fail(PTMI_ECAPACITY, "%d samples exceed one batch's 2^32 item ids", sample_count);
+  const size_t need = mk_workspace_bytes(npix, sample_count);
+  if (!workspace || !aligned16(workspace) || workspace_bytes < need)
+    return fail(PTMI_EINVAL, "workspace too small/misaligned for one batch (%zu < %zu)", workspace_bytes, need);
+  if (n_tiles == 0) return PTMI_OK;
+  return check_hip(mk_trace_staged_tiles(sc, fr, stack_needed(scene), workspace, tile_list, n_tiles, sample_begin,
+                                         sample_count, (unsigned long long*)counters, (hipStream_t)stream),
+                   "mk_trace_tiles_ws");
+}
+
+int ptmi_mk_resolve_stats_ws(const ptmi_frame* frame, const void* workspace, size_t workspace_bytes, float* accum,
+                             float* stats, const int32_t* tile_list, int32_t n_tiles, int32_t sample_count,
+                             void* stream) {
+  DevFrame fr;
+  int rc = to_dev_frame(frame, fr);
+  if (rc) return rc;
+  if (!accum) return fail(PTMI_EINVAL, "accum is NULL");
+  if (!stats || !aligned16(stats)) return fail(PTMI_EINVAL, "stats NULL/misaligned");
+  if (sample_count < 1) return fail(PTMI_EINVAL, "sample_count must be >= 1");
+  if (tile_list && (!aligned4(tile_list) || n_tiles < 0 || (int64_t)n_tiles > mk_tile_count(fr)))
+    return fail(PTMI_EINVAL, "tile_list misaligned or n_tiles %d outside [0, %lld]", n_tiles,
+                (long long)mk_tile_count(fr));
+  const int32_t npix = fr.w * fr.n_rows;
+  if (npix == 0) return PTMI_OK;
+  const size_t need = mk_workspace_bytes(npix, sample_count);
+  if (!workspace || !aligned16(workspace) || workspace_bytes < need)
+    return fail(PTMI_EINVAL, "workspace too small/misaligned for one batch (%zu < %zu)", workspace_bytes, need);
+  if (tile_list && n_tiles == 0) return PTMI_OK;
+  return check_hip(launch_stats_resolve(fr, (const float*)workspace, npix, sample_count, accum, stats, tile_list,
+                                        n_tiles, kProfMkResolve, (hipStream_t)stream),
+                   "mk_resolve_stats_ws");
+}
+
+int ptmi_wf_render_stats(const ptmi_scene_view* scene, const ptmi_frame* frame, void* workspace,
+                         size_t workspace_bytes, float* accum, float* stats, int32_t sample_begin,
+                         int32_t sample_count, uint64_t* counters, void* stream) {
+  DevScene sc;
+  DevFrame fr;
+  int rc = to_dev_scene(scene, sc);
+  if (rc) return rc;
+  if ((rc = to_dev_frame(frame, fr))) return rc;
+  if ((rc = check_traversal(sc, fr))) return rc;
+  if (!accum) return fail(PTMI_EINVAL, "accum is NULL");
+  if (!stats || !aligned16(stats)) return fail(PTMI_EINVAL, "stats NULL/misaligned");
+  if (sample_begin < 0 || sample_count < 0) return fail(PTMI_EINVAL, "bad sample range");
+  int32_t npix = fr.w * fr.n_rows;
+  if (npix == 0) return PTMI_OK;
+  if (!workspace || !aligned16(workspace) || workspace_bytes < wf_workspace_bytes(npix, 1))
+    return fail(PTMI_EINVAL, "workspace too small/misaligned (%zu < %zu)", workspace_bytes,
+                wf_workspace_bytes(npix, 1));
+  if (sample_count == 0) return PTMI_OK;
+  return check_hip(wf_render(sc, fr, stack_needed(scene), workspace, workspace_bytes, accum, sample_begin,
+                             sample_count, (unsigned long long*)counters, (hipStream_t)stream, stats),
+                   "wf_render_stats");
+}
+
+int ptmi_tile_update(const ptmi_frame* frame, const float* stats, float threshold, int32_t min_spp, int32_t max_spp,
+                     int32_t* tile_state, float* tile_err, int32_t* tile_list, int32_t* n_active, void* stream) {
+  DevFrame fr;
+  int rc = to_dev_frame(frame, fr);
+  if (rc) return rc;
+  if (!stats || !aligned16(stats)) return fail(PTMI_EINVAL, "stats NULL/misaligned");
+  if (!(threshold >= 0.0f)) return fail(PTMI_EINVAL, "threshold must be >= 0");
+  if (min_spp < 0 || max_spp < min_spp) return fail(PTMI_EINVAL, "bad spp range [%d, %d]", min_spp, max_spp);
+  if (!tile_state || !tile_err || !tile_list || !n_active || !aligned4(tile_state) || !aligned4(tile_err) ||
+      !aligned4(tile_list) || !aligned4(n_active))
+    return fail(PTMI_EINVAL, "tile buffers NULL/misaligned");
+  return check_hip(launch_tile_update(fr, stats, threshold, min_spp, max_spp, tile_state, tile_err, tile_list,
+                                      n_active, (hipStream_t)stream),
+                   "tile_update");
+}
+
+int ptmi_tonemap_stats(const float* accum, const float* stats, uint8_t* out, int32_t width, int32_t height,
+                       void* stream) {
+  if (!accum || !out || width <= 0 || height <= 0) return fail(PTMI_EINVAL, "bad tonemap arguments");
+  if (!stats || !aligned16(stats)) return fail(PTMI_EINVAL, "stats NULL/misaligned");
+  int64_t n = (int64_t)width * height * 3;
+  if (n > 0x7fffffff) return fail(PTMI_ECAPACITY, "image too large");
+  unsigned g = (unsigned)((n + kBlock - 1) / kBlock);
+  if (g > 4096) g = 4096;
+  hipLaunchKernelGGL(tonemap_stats_kernel, dim3(g), dim3(kBlock), 0, (hipStream_t)stream, accum,
+                     (const float4*)stats, out, (int32_t)n);
+  return check_hip(hipGetLastError(), "tonemap_stats launch");
 }
 
 int ptmi_prof_start(int32_t max_launches) {

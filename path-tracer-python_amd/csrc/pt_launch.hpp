@@ -25,13 +25,32 @@ hipError_t mk_render_staged(const DevScene& sc, const DevFrame& fr, int32_t stac
 hipError_t mk_trace_staged(const DevScene& sc, const DevFrame& fr, int32_t stack_needed, void* ws,
                            int32_t s_begin, int32_t nb, unsigned long long* counters, hipStream_t stream);
 int64_t mk_max_batch(const DevFrame& fr);
+// stats != nullptr: every batch resolves through launch_stats_resolve.
 hipError_t wf_render(const DevScene& sc, const DevFrame& fr, int32_t stack_needed, void* ws, size_t ws_bytes,
                      float* accum, int32_t s_begin, int32_t s_count, unsigned long long* counters,
-                     hipStream_t stream);
+                     hipStream_t stream, float* stats = nullptr);
 size_t wf_workspace_bytes(int32_t npix, int32_t batch);
 // Sets the wavefront tail threshold (capacity / divisor; 0 = no tail launch); returns the previous one.
 int32_t wf_set_drain_at(int32_t divisor);
 // accum[pixel] += staging[s][p] for s = 0..batch-1 in order (profiled as `prof_kind`).
 hipError_t launch_stage_resolve(const DevFrame& fr, const float* staging, int32_t npix, int32_t batch,
                                 float* accum, int prof_kind, hipStream_t stream);
+
+// Adaptive sampling (pt_adaptive.hip; the listed trace is pt_megakernel.hip's).
+// The staged megakernel's 64-pixel tiles of a frame: tile size and grid.
+void mk_tile_grid(const DevFrame& fr, int32_t* tile_w, int32_t* tile_h, int32_t* tiles_x, int32_t* tiles_y);
+int64_t mk_tile_count(const DevFrame& fr);
+// mk_trace_staged for the tiles of tile_list[0 .. n) only (device ids, ids outside the grid ignored).
+hipError_t mk_trace_staged_tiles(const DevScene& sc, const DevFrame& fr, int32_t stack_needed, void* ws,
+                                 const int32_t* tile_list, int32_t n, int32_t s_begin, int32_t nb,
+                                 unsigned long long* counters, hipStream_t stream);
+// launch_stage_resolve plus the Welford update of stats[pixel] = {n, mean, M2, 0};
+// tile_list == nullptr: every pixel of the frame, else the pixels of the listed tiles.
+hipError_t launch_stats_resolve(const DevFrame& fr, const float* staging, int32_t npix, int32_t batch, float* accum,
+                                float* stats, const int32_t* tile_list, int32_t n_tiles, int prof_kind,
+                                hipStream_t stream);
+// Tile errors, monotone tile states, the ascending list of active tiles and its length.
+hipError_t launch_tile_update(const DevFrame& fr, const float* stats, float threshold, int32_t min_spp,
+                              int32_t max_spp, int32_t* tile_state, float* tile_err, int32_t* tile_list,
+                              int32_t* n_active, hipStream_t stream);
 }  // namespace ptmi

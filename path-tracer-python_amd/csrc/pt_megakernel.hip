@@ -18,6 +18,10 @@
 //     does not end in a long partially-filled last round of blocks; each
 //     path writes its colour to staging[sample][pixel] and stage_resolve
 //     adds them in sample order — the same float additions as direct mode;
+//   * tile-listed staged mode (LISTED, adaptive sampling): the units cover
+//     only the tiles of a device list, mapped in locate(); the unlisted
+//     instantiations compile to the code they were without the flag
+//     (profiles/adaptive/resources.md);
 //   * BVH: child-box BVH2 nodes (80 B, one node load tests both children),
 //     traversal stack in LDS (slot-major, conflict-free), see pt_device.hpp.
 // Perlin corner loop fully unrolled here (A/B on MI355X: +2.5 % megakernel,
@@ -220,6 +224,11 @@ struct MkWork {
   FastDiv by_nb, by_tiles_x, by_len;
   int32_t nunits;    // units of the batch (multiple of csamp)
   int32_t tail_div;  // TAIL_DIV * waves of the grid
+  // tile-listed launches (mk_render_kernel's LISTED): the batch's virtual tile
+  // v is tile tile_list[v]; v >= n_list or an id outside [0, ntiles) decodes
+  // outside the frame, as the shards' padded units do
+  const int32_t* tile_list;
+  int32_t n_list, ntiles;
 };
 constexpr int kMkTile = 8;
 
@@ -241,7 +250,7 @@ static int64_t mk_tiles(const DevFrame& fr, int32_t* tx_out = nullptr) {
   return tx * ty;
 }
 
-template <int STACK, bool STAGED, int TRAV = PTMI_TRAV_STACK>
+template <int STACK, bool STAGED, int TRAV = PTMI_TRAV_STACK, bool LISTED = false>
 // waves/SIMD the LDS stack allows: 160 KiB / (STACK * 8 B * 256) blocks per CU
 // (16 -> 5, 20 -> 4, 24 -> 3, 32 -> 2), and the VGPR budget of that many
 // waves (96 at 5, 128 at 4).
@@ -302,7 +311,14 @@ __global__ __launch_bounds__(kMkBlock, stress_waves(STACK < 20 ? PTMI_MK_MIN_WAV
     if (kPersist) {
       // shard-contiguous unit numbering: shard s holds tiles s, s + S, s + 2S, ...
       const uint32_t v = k >> 6, sh = fdiv(v, wk.by_len), j = v - sh * (uint32_t)wk.shard_len;
-      const uint32_t tq = fdiv(j, wk.by_nb), t = tq * (uint32_t)kMkShards + sh, ty = fdiv(t, wk.by_tiles_x);
+      const uint32_t tq = fdiv(j, wk.by_nb);
+      uint32_t t = tq * (uint32_t)kMkShards + sh;
+      if (LISTED) {  // virtual tile -> listed tile; anything else lands below the frame's last row
+        const uint32_t id = t < (uint32_t)wk.n_list ? (uint32_t)wk.tile_list[t] : 0xffffffffu;
+        if (id >= (uint32_t)wk.ntiles) return Loc{fr.x0, fr.n_rows, s_begin + (int32_t)(j - tq * (uint32_t)wk.nb)};
+        t = id;
+      }
+      const uint32_t ty = fdiv(t, wk.by_tiles_x);
       return Loc{fr.x0 + ((int32_t)(t - ty * (uint32_t)wk.tiles_x) << wk.tw_log2), (int32_t)ty << (6 - wk.tw_log2),
                  s_begin + (int32_t)(j - tq * (uint32_t)wk.nb)};
     }
@@ -769,17 +785,22 @@ size_t mk_workspace_bytes(int32_t npix, int32_t batch) {  // staging + the shard
 // The megakernel of one staged batch: every (sample, pixel) colour of the
 // batch into staging[sample][pixel]; the accumulator is not touched (the
 // resolve is launch_stage_resolve, on the caller's schedule).
-template <int STACK, int TRAV = PTMI_TRAV_STACK>
+// LISTED: only the tiles of tile_list[0 .. n_list) are traced (units are sized
+// from the list length; staging keeps its [sample][frame pixel] layout).
+template <int STACK, int TRAV = PTMI_TRAV_STACK, bool LISTED = false>
 static hipError_t launch_mk_trace(const DevScene& sc, const DevFrame& fr, float* staging, int32_t s_begin,
-                                  int32_t nb, unsigned long long* counters, hipStream_t stream) {
+                                  int32_t nb, unsigned long long* counters, hipStream_t stream,
+                                  const int32_t* tile_list = nullptr, int32_t n_list = 0) {
   float* accum = nullptr;  // staged kernels write staging only
   int32_t tx = 0;
-  const int64_t tiles = mk_tiles(fr, &tx);
+  const int64_t frame_tiles = mk_tiles(fr, &tx);
+  const int64_t tiles = LISTED ? (int64_t)n_list : frame_tiles;  // tiles the units cover
+  const int64_t batch_samples = (LISTED ? 64 * tiles : (int64_t)fr.w * fr.n_rows) * nb;
   int dev = 0, ncu = 0, per_cu = 0;
   hipError_t e0 = hipGetDevice(&dev);
   if (e0 == hipSuccess) e0 = hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
   if (e0 == hipSuccess)
-    e0 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, mk_render_kernel<STACK, true, TRAV>, kMkBlock, 0);
+    e0 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, mk_render_kernel<STACK, true, TRAV, LISTED>, kMkBlock, 0);
   if (e0 != hipSuccess) return e0;
   MkWork wk;
   wk.ctl = (int32_t*)((char*)staging + mk_staging_bytes(fr.w * fr.n_rows, nb));
@@ -787,6 +808,9 @@ static hipError_t launch_mk_trace(const DevScene& sc, const DevFrame& fr, float*
   wk.tiles_x = tx;
   wk.tw_log2 = 6 - mk_tile_rows_log2(fr);
   wk.nb = nb;
+  wk.tile_list = tile_list;
+  wk.n_list = n_list;
+  wk.ntiles = (int32_t)frame_tiles;
   if (tiles * nb * 64 >= (1ll << 32)) return hipErrorInvalidValue;  // item ids are 32-bit
   // shard s: tiles s, s + S, ... (interleaved across the image, so every shard
   // costs about the same); virtual units past the last tile decode to rows
@@ -799,7 +823,7 @@ static hipError_t launch_mk_trace(const DevScene& sc, const DevFrame& fr, float*
   wk.by_tiles_x = fast_div((uint32_t)wk.tiles_x);
   // Small batches (an 8-rank tile shard) run on a smaller persistent grid, so
   // the next overlapped call's waves share the chip while this one drains.
-  if ((int64_t)fr.w * fr.n_rows * nb < PTMI_MK_SMALL_GRID_BATCH && per_cu > PTMI_MK_SMALL_WPC) per_cu = PTMI_MK_SMALL_WPC;
+  if (batch_samples < PTMI_MK_SMALL_GRID_BATCH && per_cu > PTMI_MK_SMALL_WPC) per_cu = PTMI_MK_SMALL_WPC;
   int64_t waves = (int64_t)(per_cu > 0 ? per_cu : 1) * (ncu > 0 ? ncu : 1);
   const int64_t chunks = wk.nunits;
   if (waves > chunks) waves = chunks;
@@ -807,12 +831,17 @@ static hipError_t launch_mk_trace(const DevScene& sc, const DevFrame& fr, float*
   // shard: 5 M samples per call for vol2 at 8 GPUs) are all tail: halving the
   // divisor there takes larger fetches, so a wave changes tile less often
   // (A/B, 8-rank rehearsal: +2 % per GPU; profiles/r03/ab/ab_mk_small_calls.log).
-  const int64_t tail = (int64_t)fr.w * fr.n_rows * nb < PTMI_MK_SMALL_BATCH ? PTMI_MK_TAIL_DIV_SMALL : PTMI_MK_TAIL_DIV;
+  const int64_t tail = batch_samples < PTMI_MK_SMALL_BATCH ? PTMI_MK_TAIL_DIV_SMALL : PTMI_MK_TAIL_DIV;
   const int64_t tdiv = tail * waves / kMkShards;
   wk.tail_div = (int32_t)(tdiv > 1 ? tdiv : 1);
-  (void)hipMemsetAsync(wk.ctl, 0, 256 * kMkShards, stream);
+  if (LISTED) {  // new code checks the memset; the unlisted path keeps its behaviour
+    e0 = hipMemsetAsync(wk.ctl, 0, 256 * kMkShards, stream);
+    if (e0 != hipSuccess) return e0;
+  } else {
+    (void)hipMemsetAsync(wk.ctl, 0, 256 * kMkShards, stream);
+  }
   const int pslot = prof_begin(kProfMk, stream);
-  hipLaunchKernelGGL((mk_render_kernel<STACK, true, TRAV>), dim3((unsigned)waves), dim3(kMkBlock), 0, stream,
+  hipLaunchKernelGGL((mk_render_kernel<STACK, true, TRAV, LISTED>), dim3((unsigned)waves), dim3(kMkBlock), 0, stream,
                      sc, fr, accum, s_begin, nb, nb, staging, counters, wk);
   prof_end(pslot, stream);
   return hipGetLastError();
@@ -833,6 +862,35 @@ hipError_t mk_trace_staged(const DevScene& sc, const DevFrame& fr, int32_t stack
   if (stack_needed <= kRefStackSlots - 1) return launch_mk_trace<64>(sc, fr, st, s_begin, nb, counters, stream);
   // leaf depth > 62: the reference's 64-entry stack drops pushes (TravRS)
   return launch_mk_trace<kRefStackSlots, kTravRefStack>(sc, fr, st, s_begin, nb, counters, stream);
+}
+
+hipError_t mk_trace_staged_tiles(const DevScene& sc, const DevFrame& fr, int32_t stack_needed, void* ws,
+                                 const int32_t* tl, int32_t n, int32_t s_begin, int32_t nb,
+                                 unsigned long long* counters, hipStream_t stream) {
+  float* st = (float*)ws;
+  if (fr.traversal == PTMI_TRAV_STACKLESS)
+    return launch_mk_trace<1, PTMI_TRAV_STACKLESS, true>(sc, fr, st, s_begin, nb, counters, stream, tl, n);
+  if (stack_needed <= PTMI_MK_STAGED_MIN_STACK)
+    return launch_mk_trace<16, PTMI_TRAV_STACK, true>(sc, fr, st, s_begin, nb, counters, stream, tl, n);
+  if (stack_needed == 17) return launch_mk_trace<17, PTMI_TRAV_STACK, true>(sc, fr, st, s_begin, nb, counters, stream, tl, n);
+  if (stack_needed == 18) return launch_mk_trace<18, PTMI_TRAV_STACK, true>(sc, fr, st, s_begin, nb, counters, stream, tl, n);
+  if (stack_needed == 19) return launch_mk_trace<19, PTMI_TRAV_STACK, true>(sc, fr, st, s_begin, nb, counters, stream, tl, n);
+  if (stack_needed <= 20) return launch_mk_trace<20, PTMI_TRAV_STACK, true>(sc, fr, st, s_begin, nb, counters, stream, tl, n);
+  if (stack_needed <= 24) return launch_mk_trace<24, PTMI_TRAV_STACK, true>(sc, fr, st, s_begin, nb, counters, stream, tl, n);
+  if (stack_needed <= 32) return launch_mk_trace<32, PTMI_TRAV_STACK, true>(sc, fr, st, s_begin, nb, counters, stream, tl, n);
+  if (stack_needed <= kRefStackSlots - 1)
+    return launch_mk_trace<64, PTMI_TRAV_STACK, true>(sc, fr, st, s_begin, nb, counters, stream, tl, n);
+  return launch_mk_trace<kRefStackSlots, kTravRefStack, true>(sc, fr, st, s_begin, nb, counters, stream, tl, n);
+}
+
+void mk_tile_grid(const DevFrame& fr, int32_t* tile_w, int32_t* tile_h, int32_t* tiles_x, int32_t* tiles_y) {
+  const int hl = mk_tile_rows_log2(fr);
+  int32_t tx = 0;
+  const int64_t tiles = mk_tiles(fr, &tx);
+  *tile_w = 64 >> hl;
+  *tile_h = 1 << hl;
+  *tiles_x = tx;
+  *tiles_y = tx > 0 ? (int32_t)(tiles / tx) : 0;
 }
 
 int64_t mk_max_batch(const DevFrame& fr) {

@@ -1175,14 +1175,18 @@ static_assert((PTMI_WF_MAX_BLOCKS / kPipes) % kShards == 0, "a pipe's grid must 
 // and the pool is empty, join, resolve.
 template <int STACK, int TRAV = PTMI_TRAV_STACK>
 static hipError_t wf_batch(const DevScene& sc, const DevFrame& fr, const WfBufs* wbs, float* accum, int32_t batch,
-                           unsigned long long* counters, hipStream_t stream, const PipeStreams& ps) {
+                           unsigned long long* counters, hipStream_t stream, const PipeStreams& ps,
+                           float* stats) {
   // a pipe's grid = a multiple of kShards, so block b's shard is b % kShards
   int64_t blocks = wbs[0].capacity / kWfBlock;
   if (blocks > PTMI_WF_MAX_BLOCKS / kPipes) blocks = PTMI_WF_MAX_BLOCKS / kPipes;
   const unsigned g = (unsigned)blocks;
   // the tail launch: one lane per continuing ray (<= capacity + the bins' padding)
   const unsigned gd = (unsigned)((wbs[0].capacity + 64 * (kBins + 1) + kWfBlock - 1) / kWfBlock);
-  (void)hipMemsetAsync(wbs[0].next, 0, kCtlWords * sizeof(int32_t), stream);
+  {  // the stats path (ptmi_wf_render_stats) checks the memset; plain renders keep their behaviour
+    const hipError_t em = hipMemsetAsync(wbs[0].next, 0, kCtlWords * sizeof(int32_t), stream);
+    if (stats && em != hipSuccess) return em;
+  }
   {
     const int pslot = prof_begin(kProfWfGenerate, stream);
     hipLaunchKernelGGL(wf_generate, dim3(1), dim3(64), 0, stream, wbs[0]);
@@ -1285,6 +1289,9 @@ static hipError_t wf_batch(const DevScene& sc, const DevFrame& fr, const WfBufs*
     if (err == hipSuccess) err = e;
   }
   if (err != hipSuccess) return err;
+  if (stats)
+    return launch_stats_resolve(fr, wbs[0].staging, wbs[0].npix, batch, accum, stats, nullptr, 0, kProfWfResolve,
+                                stream);
   return launch_stage_resolve(fr, wbs[0].staging, wbs[0].npix, batch, accum, kProfWfResolve, stream);
 }
 
@@ -1320,7 +1327,7 @@ size_t wf_workspace_bytes(int32_t npix, int32_t batch) {
 
 hipError_t wf_render(const DevScene& sc, const DevFrame& fr, int32_t stack_needed, void* ws, size_t ws_bytes,
                      float* accum, int32_t s_begin, int32_t s_count, unsigned long long* counters,
-                     hipStream_t stream) {
+                     hipStream_t stream, float* stats) {
   const int32_t npix = fr.w * fr.n_rows;
   // work items (sample, pixel) of a batch are ids below 2^31 (FastDiv's
   // range, and the kFresh bit), padded ids included: 64 per 8x8 pixel square,
@@ -1386,13 +1393,13 @@ hipError_t wf_render(const DevScene& sc, const DevFrame& fr, int32_t stack_neede
       wb.by_sqx = fast_div((uint32_t)wb.sq_x);
     }
     hipError_t e;
-    if (fr.traversal == PTMI_TRAV_STACKLESS) e = wf_batch<1, PTMI_TRAV_STACKLESS>(sc, fr, wbs, accum, nb, counters, stream, *ps);
-    else if (stack_needed <= 16) e = wf_batch<16>(sc, fr, wbs, accum, nb, counters, stream, *ps);
-    else if (stack_needed <= 20) e = wf_batch<20>(sc, fr, wbs, accum, nb, counters, stream, *ps);
-    else if (stack_needed <= 24) e = wf_batch<24>(sc, fr, wbs, accum, nb, counters, stream, *ps);
-    else if (stack_needed <= 32) e = wf_batch<32>(sc, fr, wbs, accum, nb, counters, stream, *ps);
-    else if (stack_needed <= kRefStackSlots - 1) e = wf_batch<64>(sc, fr, wbs, accum, nb, counters, stream, *ps);
-    else e = wf_batch<kRefStackSlots, kTravRefStack>(sc, fr, wbs, accum, nb, counters, stream, *ps);  // leaf depth > 62
+    if (fr.traversal == PTMI_TRAV_STACKLESS) e = wf_batch<1, PTMI_TRAV_STACKLESS>(sc, fr, wbs, accum, nb, counters, stream, *ps, stats);
+    else if (stack_needed <= 16) e = wf_batch<16>(sc, fr, wbs, accum, nb, counters, stream, *ps, stats);
+    else if (stack_needed <= 20) e = wf_batch<20>(sc, fr, wbs, accum, nb, counters, stream, *ps, stats);
+    else if (stack_needed <= 24) e = wf_batch<24>(sc, fr, wbs, accum, nb, counters, stream, *ps, stats);
+    else if (stack_needed <= 32) e = wf_batch<32>(sc, fr, wbs, accum, nb, counters, stream, *ps, stats);
+    else if (stack_needed <= kRefStackSlots - 1) e = wf_batch<64>(sc, fr, wbs, accum, nb, counters, stream, *ps, stats);
+    else e = wf_batch<kRefStackSlots, kTravRefStack>(sc, fr, wbs, accum, nb, counters, stream, *ps, stats);  // leaf depth > 62
     if (e != hipSuccess) return e;
   }
   return hipSuccess;

@@ -11,7 +11,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('PTMI_LIB') or os.path.join(_HERE, '_lib', 'libptmi.so')  # PTMI_LIB: A/B builds
-ABI_VERSION = 7  # PTMI_ABI_VERSION of include/ptmi.h
+ABI_VERSION = 8  # PTMI_ABI_VERSION of include/ptmi.h
 MAX_IMAGES = 16
 NUM_COUNTERS = 6
 COUNTER_TAIL_SEGMENTS = 5  # wavefront segments traced in the tail launch (wf_drain), part of [0]
@@ -57,7 +57,10 @@ TRAVERSALS = {'stack': 0, 'stackless': 1}
 EXPORTS = ('ptmi_version', 'ptmi_last_error', 'ptmi_scene_check', 'ptmi_mk_render', 'ptmi_mk_workspace_bytes',
            'ptmi_mk_render_ws', 'ptmi_mk_trace_ws', 'ptmi_mk_max_batch', 'ptmi_mk_resolve_ws', 'ptmi_wf_workspace_bytes',
            'ptmi_wf_render', 'ptmi_clear', 'ptmi_tonemap', 'ptmi_bvh_build_sah', 'ptmi_prof_start',
-           'ptmi_prof_stop', 'ptmi_prof_stop_busy', 'ptmi_node_bytes', 'ptmi_wf_set_drain_at')
+           'ptmi_prof_stop', 'ptmi_prof_stop_busy', 'ptmi_node_bytes', 'ptmi_wf_set_drain_at',
+           # ABI v8: per-pixel error estimates and adaptive tile sampling
+           'ptmi_mk_tile_grid', 'ptmi_stats_clear', 'ptmi_mk_trace_tiles_ws', 'ptmi_mk_resolve_stats_ws',
+           'ptmi_wf_render_stats', 'ptmi_tile_update', 'ptmi_tonemap_stats')
 PROF_KINDS = ('megakernel', 'wf_generate', 'wf_intersect', 'wf_drain', 'wf_scatter', 'wf_resolve', 'mk_resolve')
 
 _lib = None
@@ -111,6 +114,16 @@ def load(path: str = LIB_PATH):
     lib.ptmi_tonemap.argtypes = [P, P, C.c_int32, C.c_int32, C.c_int32, P]
     lib.ptmi_bvh_build_sah.argtypes = [P, C.c_int32, P, C.c_int32, P, C.c_int32, P, P, P, P, P, P, P,
                                        C.POINTER(C.c_int32)]
+    I32P = C.POINTER(C.c_int32)
+    lib.ptmi_mk_tile_grid.argtypes = [C.POINTER(Frame), I32P, I32P, I32P, I32P]
+    lib.ptmi_stats_clear.argtypes = [C.POINTER(Frame), P, P]
+    lib.ptmi_mk_trace_tiles_ws.argtypes = [C.POINTER(SceneView), C.POINTER(Frame), P, C.c_size_t, P, C.c_int32,
+                                           C.c_int32, C.c_int32, P, P]
+    lib.ptmi_mk_resolve_stats_ws.argtypes = [C.POINTER(Frame), P, C.c_size_t, P, P, P, C.c_int32, C.c_int32, P]
+    lib.ptmi_wf_render_stats.argtypes = [C.POINTER(SceneView), C.POINTER(Frame), P, C.c_size_t, P, P, C.c_int32,
+                                         C.c_int32, P, P]
+    lib.ptmi_tile_update.argtypes = [C.POINTER(Frame), P, C.c_float, C.c_int32, C.c_int32, P, P, P, P, P]
+    lib.ptmi_tonemap_stats.argtypes = [P, P, P, C.c_int32, C.c_int32, P]
     lib.ptmi_prof_start.argtypes = [C.c_int32]
     lib.ptmi_prof_stop.argtypes = [P, P, C.c_int32]
     lib.ptmi_prof_stop_busy.argtypes = [P, P, P, C.c_int32]

@@ -317,15 +317,123 @@ class Integrator:
             _lib.check(self.lib.ptmi_clear(C.byref(frame), C.c_void_p(accum.data_ptr()), self._stream(stream)),
                        'ptmi_clear')
 
-    def tonemap(self, accum, spp, stream=None):
+    def tonemap(self, accum, spp=None, stats=None, stream=None):
+        """u8 image of accum divided by ``spp``, or, with ``stats``, by each
+        pixel's own sample count (ptmi_tonemap_stats)."""
         if accum.device != self.scene.device:
             raise _lib.PtmiError(f'accum is on {accum.device}, the scene on {self.scene.device}')
+        if (spp is None) == (stats is None):
+            raise _lib.PtmiError('tonemap needs exactly one of spp and stats')
         h, w, _ = accum.shape
         with self._dev():
             out = torch.empty((h, w, 3), dtype=torch.uint8, device=accum.device)
+            if stats is not None:
+                _check_stats(stats, h, w, self.scene.device)
+                _lib.check(self.lib.ptmi_tonemap_stats(C.c_void_p(accum.data_ptr()), C.c_void_p(stats.data_ptr()),
+                                                       C.c_void_p(out.data_ptr()), w, h, self._stream(stream)),
+                           'ptmi_tonemap_stats')
+                return out
             _lib.check(self.lib.ptmi_tonemap(C.c_void_p(accum.data_ptr()), C.c_void_p(out.data_ptr()), w, h,
                                              int(spp), self._stream(stream)), 'ptmi_tonemap')
         return out
+
+    # ------------------------------------------ error estimates, adaptive tiles
+    def tile_grid(self, frame):
+        """(tile_w, tile_h, tiles_x, tiles_y) of the frame's 64-pixel megakernel tiles."""
+        v = [C.c_int32() for _ in range(4)]
+        _lib.check(self.lib.ptmi_mk_tile_grid(C.byref(frame), *[C.byref(x) for x in v]), 'ptmi_mk_tile_grid')
+        return tuple(int(x.value) for x in v)
+
+    def new_stats(self, frame):
+        """A zeroed stats buffer ({n, mean, M2, 0} per pixel) for the frame's image."""
+        return torch.zeros((frame.height, frame.width, 4), dtype=torch.float32, device=self.scene.device)
+
+    def new_tiles(self, frame):
+        """Tile buffers of a frame: state (all active), error, active list and its length."""
+        _, _, tx, ty = self.tile_grid(frame)
+        dev = self.scene.device
+        return {'state': torch.ones(tx * ty, dtype=torch.int32, device=dev),
+                'err': torch.full((tx * ty,), float('inf'), dtype=torch.float32, device=dev),
+                'list': torch.arange(tx * ty, dtype=torch.int32, device=dev), 'n': tx * ty, 'grid': (tx, ty)}
+
+    def clear_stats(self, frame, stats, stream=None):
+        _check_stats(stats, frame.height, frame.width, self.scene.device)
+        with self._dev():
+            _lib.check(self.lib.ptmi_stats_clear(C.byref(frame), C.c_void_p(stats.data_ptr()), self._stream(stream)),
+                       'ptmi_stats_clear')
+
+    def render_mk_stats(self, frame, accum, stats, sample_begin, sample_count, tiles=None, stream=None):
+        """Megakernel samples [sample_begin, sample_begin + sample_count) added
+        into accum in sample order and into stats (Welford on the luminance):
+        always the staged trace plus the stats resolve, single samples
+        included. ``tiles``: None for the whole frame, or (int32 device tensor
+        of tile ids, count): only those tiles are traced and resolved."""
+        _check_accum(accum, frame, self.scene.device)
+        _check_stats(stats, frame.height, frame.width, self.scene.device)
+        sample_count = int(sample_count)
+        tl, nt = (None, 0) if tiles is None else tiles
+        if tl is not None:
+            nt = int(nt)
+            if not (isinstance(tl, torch.Tensor) and tl.dtype == torch.int32 and tl.is_contiguous()
+                    and tl.device == self.scene.device and 0 <= nt <= tl.numel()):
+                raise _lib.PtmiError('tiles must be (contiguous int32 tensor on the scene device, count <= its length)')
+        npix = frame.w * len(frame_pixel_rows(frame))
+        if npix == 0 or sample_count <= 0 or (tl is not None and nt == 0):
+            return
+        max_batch = int(self.lib.ptmi_mk_max_batch(C.byref(frame)))
+        if max_batch < 1:
+            _lib.check(-1, 'ptmi_mk_max_batch')
+        per = max(1, min(sample_count, self.STAGING_BYTES // max(1, 12 * npix), max_batch))
+        with self._dev():
+            ws = self.workspace(frame, per, 'mk')
+            wp, sp = C.c_void_p(ws.data_ptr()), self._stream(stream)
+            for b in range(0, sample_count, per):
+                n = min(per, sample_count - b)
+                if tl is None:
+                    _lib.check(self.lib.ptmi_mk_trace_ws(C.byref(self.scene.view), C.byref(frame), wp, self._ws_bytes,
+                                                         int(sample_begin) + b, n, self._cnt(), sp),
+                               'ptmi_mk_trace_ws')
+                else:
+                    _lib.check(self.lib.ptmi_mk_trace_tiles_ws(C.byref(self.scene.view), C.byref(frame), wp,
+                                                               self._ws_bytes, C.c_void_p(tl.data_ptr()), nt,
+                                                               int(sample_begin) + b, n, self._cnt(), sp),
+                               'ptmi_mk_trace_tiles_ws')
+                _lib.check(self.lib.ptmi_mk_resolve_stats_ws(C.byref(frame), wp, self._ws_bytes,
+                                                             C.c_void_p(accum.data_ptr()),
+                                                             C.c_void_p(stats.data_ptr()),
+                                                             C.c_void_p(tl.data_ptr()) if tl is not None else None,
+                                                             nt, n, sp), 'ptmi_mk_resolve_stats_ws')
+
+    def render_wf_stats(self, frame, accum, stats, sample_begin, sample_count, stream=None):
+        """render_wf resolving through the stats resolve (whole frame only)."""
+        _check_accum(accum, frame, self.scene.device)
+        _check_stats(stats, frame.height, frame.width, self.scene.device)
+        with self._dev():
+            ws = self.workspace(frame, sample_count)
+            _lib.check(self.lib.ptmi_wf_render_stats(C.byref(self.scene.view), C.byref(frame),
+                                                     C.c_void_p(ws.data_ptr()), self._ws_bytes,
+                                                     C.c_void_p(accum.data_ptr()), C.c_void_p(stats.data_ptr()),
+                                                     int(sample_begin), int(sample_count), self._cnt(),
+                                                     self._stream(stream)), 'ptmi_wf_render_stats')
+
+    def tile_update(self, frame, stats, threshold, min_spp, max_spp, tiles, stream=None):
+        """Tile errors and states from stats (ptmi_tile_update) into the
+        buffers of ``tiles`` (new_tiles); returns the number of active tiles
+        (one 4-byte readback) and stores it as tiles['n']."""
+        _check_stats(stats, frame.height, frame.width, self.scene.device)
+        if getattr(self, '_n_active', None) is None:
+            self._n_active = torch.zeros(1, dtype=torch.int32, device=self.scene.device)
+        with self._dev():
+            _lib.check(self.lib.ptmi_tile_update(C.byref(frame), C.c_void_p(stats.data_ptr()), float(threshold),
+                                                 int(min_spp), int(max_spp), C.c_void_p(tiles['state'].data_ptr()),
+                                                 C.c_void_p(tiles['err'].data_ptr()),
+                                                 C.c_void_p(tiles['list'].data_ptr()),
+                                                 C.c_void_p(self._n_active.data_ptr()), self._stream(stream)),
+                       'ptmi_tile_update')
+            if stream is not None:
+                stream.synchronize()
+            tiles['n'] = int(self._n_active.item())
+        return tiles['n']
 
     def _after_traces(self, stream):
         """Make `stream` wait for the overlapped traces in flight: they add to
@@ -369,6 +477,14 @@ class Integrator:
                 for side in ov['streams']:
                     side.wait_event(ev)
             self._reset_event = ev  # side streams created after this reset wait on it too
+
+
+def _check_stats(stats, height, width, device=None):
+    if not (isinstance(stats, torch.Tensor) and stats.is_cuda and stats.dtype == torch.float32
+            and stats.is_contiguous() and tuple(stats.shape) == (height, width, 4)):
+        raise _lib.PtmiError(f'stats must be a contiguous cuda float32 tensor of shape ({height}, {width}, 4)')
+    if device is not None and stats.device != device:
+        raise _lib.PtmiError(f'stats is on {stats.device}, the scene on {device}')
 
 
 def _check_accum(accum, frame, device=None):

@@ -87,6 +87,8 @@ class InteractiveViewer(MI355XRenderer):
         self.sample_times = []
         self.render_start_time = time.time()
         self.clear_accumulation_buffer()
+        if self.stats is not None:  # a render with target_error: error estimates and tile states start over too
+            self._adaptive_reset()
         self.integrator.reset_counters()
         self.is_rendering_active = True
         print(f"\n{'─' * 60}\nCamera rotated - restarting render from sample 0\n{'─' * 60}")
@@ -122,9 +124,14 @@ class InteractiveViewer(MI355XRenderer):
         return None
 
     # ------------------------------------------------------------ rendering
-    def render_interactive(self):
+    def render_interactive(self, target_error=None, min_spp=16):
         """Progressive render to cam.samples_per_pixel, then write the image
-        (interactive_viewer.py:327-451, headless)."""
+        (interactive_viewer.py:327-451, headless). With ``target_error`` the
+        samples accumulate through the stats path (per-pixel error estimates,
+        MI355XRenderer.render_adaptive) and the render stops early once every
+        tile has min_spp samples and an error of at most target_error; the
+        image then divides by the samples rendered. target_error=None is the
+        reference's behaviour."""
         import torch
         spp = int(self.cam.samples_per_pixel)
         print('\nInteractiveViewer')
@@ -135,6 +142,10 @@ class InteractiveViewer(MI355XRenderer):
         self.render_sample(0)  # warm-up sample, cleared (interactive_viewer.py:355-359)
         torch.cuda.synchronize(self.dscene.device)
         self.clear_accumulation_buffer()
+        if target_error is not None:
+            self._integrator_label = 'adaptive-megakernel'
+            self._adaptive = None  # no pass schedule: not resumable as a render_adaptive() run
+            self._adaptive_reset()
         self.integrator.reset_counters()
         print(f'  Kernel Warmup: {(time.time() - t0) * 1000:6.2f}ms')
         self.setup_interactive_preview()
@@ -147,7 +158,11 @@ class InteractiveViewer(MI355XRenderer):
             if self.current_sample == 0:
                 n = 1  # the reference prints sample 1
             t = time.time()
-            self.integrator.render_mk(self.frame, self.accum, self.current_sample, n)
+            if target_error is None:
+                self.integrator.render_mk(self.frame, self.accum, self.current_sample, n)
+            else:
+                self.integrator.render_mk_stats(self.frame, self.accum, self.stats, self.current_sample, n)
+                left = self.integrator.tile_update(self.frame, self.stats, target_error, min_spp, spp, self._tiles)
             torch.cuda.synchronize(self.dscene.device)
             dt = (time.time() - t) / n
             self.sample_times += [dt] * n
@@ -158,6 +173,11 @@ class InteractiveViewer(MI355XRenderer):
             print(f'{self.current_sample:4d}/{spp} ({self.current_sample / spp * 100:5.1f}%) │ {dt * 1000:5.1f}ms │ '
                   f'Elapsed: {elapsed:5.1f}s │ Throughput: {thr / 1e6:5.2f}M pix/s │ '
                   f'ETA: {(spp - self.current_sample) * avg:4.1f}s')
+            if target_error is not None and left == 0 and self.current_sample < spp:
+                print(f"{'─' * 60}\n✓ Every tile within the target error {target_error:g} "
+                      f'after {self.current_sample} samples')
+                self.is_rendering_active = False
+                break
         if self.current_sample >= spp:
             print(f"{'─' * 60}\n✓ Reached max samples ({spp})")
             self.is_rendering_active = False

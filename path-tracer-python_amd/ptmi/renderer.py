@@ -22,6 +22,13 @@ the render state; ``load_checkpoint(path)`` followed by ``render(resume=True)``
 finishes the remaining samples. Samples are keyed by (seed, pixel, sample) and
 added in sample order, so the resumed image is bit-identical to an
 uninterrupted render.
+
+Adaptive sampling (no counterpart in the reference either): ``render_adaptive``
+keeps per-pixel {n, mean, M2} of the sample luminance next to the accumulator
+and renders passes of the 64-pixel tiles whose error estimate is still above
+a target; ``noise_map()`` / ``sample_count_map()`` expose the estimates, the
+image divides each pixel by its own sample count, and checkpoints carry the
+extra state.
 """
 from __future__ import annotations
 
@@ -61,6 +68,11 @@ class MI355XRenderer:
         self.checkpoint_path = None
         self.checkpoint_every = 1
         self._resume_state = None
+        # adaptive sampling (render_adaptive): per-pixel stats, tile buffers, parameters, per-pass log
+        self.stats = None
+        self._tiles = None
+        self._adaptive = None
+        self.adaptive_passes = []
         # launches per progress report: one launch renders many samples (path regeneration)
         self.samples_per_launch = int(samples_per_launch)
         device.require_gpu()
@@ -168,6 +180,109 @@ class MI355XRenderer:
         """Wavefront render (renderer.py:249-359)."""
         self._run(self.integrator.render_wf, 'wavefront', resume)
 
+    # --------------------------------------------------------------- adaptive
+    def _adaptive_reset(self):
+        """Zeroed stats and all tiles active, for the current frame."""
+        H, W = self.cam.img_height, self.cam.img_width
+        if self.stats is None or tuple(self.stats.shape[:2]) != (H, W):
+            self.stats = self.integrator.new_stats(self.frame)
+        else:
+            self.integrator.clear_stats(self.frame, self.stats)
+        self._tiles = self.integrator.new_tiles(self.frame)
+
+    def render_adaptive(self, target_error, pass_spp=None, min_spp=16, max_spp=None, integrator='megakernel',
+                        resume=False, enable_preview: bool = True):
+        """Adaptive render (no counterpart in the reference, which always runs
+        cam.samples_per_pixel samples of every pixel). Pass k renders samples
+        [k * pass_spp, (k + 1) * pass_spp) of the tiles still active, through
+        the stats path (per-pixel {n, mean, M2} of the sample luminance), then
+        updates the tiles: a tile is done once it has min_spp samples and its
+        error (the mean relative standard error of its pixels' luminance) is
+        at most target_error, or at max_spp samples (default
+        cam.samples_per_pixel). Stops when no tile is active. A tile whose
+        error is NaN (a NaN sample) is done. integrator='wavefront' renders the
+        whole frame every pass; only the stop is adaptive. Single device only
+        (band_stride == 1). The image divides each pixel by its own sample
+        count. resume=True continues a load_checkpoint() state bit-identically."""
+        import torch
+        if integrator not in ('megakernel', 'wavefront'):
+            raise ValueError(f'unknown integrator {integrator!r}')
+        self._integrator_label = 'adaptive-' + integrator
+        self._upload_camera()
+        if self.frame.band_stride != 1:
+            raise ValueError('render_adaptive needs band_stride == 1 (multi-GPU adaptive sampling is out of scope)')
+        max_spp = int(self.cam.samples_per_pixel if max_spp is None else max_spp)
+        min_spp = int(min_spp)
+        pass_spp = int(pass_spp if pass_spp is not None else max(1, min_spp))
+        target_error = float(np.float32(target_error))
+        if not target_error >= 0.0 or pass_spp < 1 or min_spp < 0 or max_spp < min_spp:
+            raise ValueError('render_adaptive needs target_error >= 0, pass_spp >= 1 and 0 <= min_spp <= max_spp')
+        self._adaptive = {'target_error': target_error, 'pass_spp': pass_spp, 'min_spp': min_spp, 'max_spp': max_spp}
+        integ = self.integrator
+        mk = integrator == 'megakernel'
+        t0 = time.time()
+        if resume:
+            if self._resume_state is None:
+                raise ValueError('render_adaptive(resume=True) needs load_checkpoint() first')
+            self._check_resume_state()
+        else:
+            (integ.render_mk if mk else integ.render_wf)(self.frame, self.accum, 0, 1)  # warm-up sample, then cleared
+            torch.cuda.synchronize(self.dscene.device)
+            self.clear_accumulation_buffer()
+            self._adaptive_reset()
+            self.current_sample = 0
+            self.adaptive_passes = []
+        self._resume_state = None
+        integ.reset_counters()
+        torch.cuda.synchronize(self.dscene.device)
+        self.timing['kernel_warmup'] = time.time() - t0
+        tiles = self._tiles
+        ntiles = tiles['grid'][0] * tiles['grid'][1]
+        print(f'\n{self.__class__.__name__} (adaptive {integrator})')
+        print(f'Resolution: {self.cam.img_width}x{self.cam.img_height} | Samples: {min_spp}..{max_spp} in passes of '
+              f'{pass_spp} | Target error: {target_error:g} | Depth: {self.max_depth}')
+        self.render_start_time = time.time()
+        while tiles['n'] > 0 and self.current_sample < max_spp:
+            n = min(pass_spp, max_spp - self.current_sample)
+            active = tiles['n']
+            t = time.time()
+            if mk:
+                integ.render_mk_stats(self.frame, self.accum, self.stats, self.current_sample, n,
+                                      None if active == ntiles else (tiles['list'], active))
+            else:
+                integ.render_wf_stats(self.frame, self.accum, self.stats, self.current_sample, n)
+            integ.tile_update(self.frame, self.stats, target_error, min_spp, max_spp, tiles)
+            torch.cuda.synchronize(self.dscene.device)
+            dt = time.time() - t
+            self.sample_times += [dt / n] * n
+            self.current_sample += n
+            traced = (64 * active if mk else self.cam.img_width * self.cam.img_height) * n
+            self.adaptive_passes.append({'pass': len(self.adaptive_passes), 'active_tiles': active, 'samples': n,
+                                         'traced': traced, 'seconds': dt, 'active_after': tiles['n']})
+            print(f'pass {len(self.adaptive_passes):3d} | {self.current_sample:5d}/{max_spp} spp | '
+                  f'{active:6d}/{ntiles} tiles | {dt * 1e3:8.2f} ms | {tiles["n"]:6d} tiles left')
+            if self.checkpoint_path and tiles['n'] > 0 and self.current_sample < max_spp and \
+                    len(self.adaptive_passes) % max(1, self.checkpoint_every) == 0:
+                self.save_checkpoint(self.checkpoint_path)
+        self.write_image()
+        self.print_statistics()
+
+    def noise_map(self):
+        """Tile errors of the last tile update, (tiles_y, tiles_x) f32 (+inf before any update)."""
+        if self._tiles is None:
+            raise ValueError('no adaptive render yet')
+        tx, ty = self._tiles['grid']
+        return self._tiles['err'].cpu().numpy().reshape(ty, tx)
+
+    def sample_count_map(self):
+        """Samples accumulated per pixel through the stats path, (height, width) int32."""
+        if self.stats is None:
+            raise ValueError('no adaptive render yet')
+        return self.stats[..., 0].cpu().numpy().astype(np.int32)
+
+    def _is_adaptive(self):
+        return self._integrator_label.startswith('adaptive-') and self.stats is not None
+
     # ------------------------------------------------------- checkpoint/resume
     # what must match for a checkpoint to continue this render exactly; the
     # integrator too: megakernel and wavefront paths differ (Q1, Q11, Q14), so
@@ -200,6 +315,14 @@ class MI355XRenderer:
         torch.cuda.synchronize(self.dscene.device)
         st = self._render_state()
         acc = self.accum.cpu().numpy()
+        if self._is_adaptive() and self._adaptive is not None:  # stats, tile state and the adaptive parameters too
+            a = self._adaptive
+            st.update(stats=self.stats.cpu().numpy(), tile_state=self._tiles['state'].cpu().numpy(),
+                      tile_err=self._tiles['err'].cpu().numpy(),
+                      adaptive=np.array([a['target_error'], a['pass_spp'], a['min_spp'], a['max_spp']], np.float64),
+                      adaptive_passes=np.array([[q['active_tiles'], q['samples'], q['traced'], q['active_after']]
+                                                for q in self.adaptive_passes], np.int64).reshape(-1, 4),
+                      adaptive_seconds=np.array([q['seconds'] for q in self.adaptive_passes], np.float64))
         d = os.path.dirname(os.path.abspath(path))
         fd, tmp = tempfile.mkstemp(prefix='.ckpt-', suffix='.npz', dir=d)
         try:
@@ -225,11 +348,28 @@ class MI355XRenderer:
             state = {k: z[k].copy() for k in self._STATE_KEYS}
             acc = z['accum'].copy()
             nxt = int(z['next_sample'])
+            ad = {k: z[k].copy() for k in ('stats', 'tile_state', 'tile_err', 'adaptive', 'adaptive_passes',
+                                           'adaptive_seconds')} if 'adaptive' in z.files else None
         if acc.dtype != np.float32 or acc.ndim != 3 or acc.shape[2] != 3:
             raise ValueError(f'checkpoint accumulator has shape {acc.shape} / {acc.dtype}')
         self.accum = torch.from_numpy(acc).to(self.dscene.device)
         self.current_sample = nxt
         self._resume_state = state
+        if ad is not None:  # an adaptive render's checkpoint: render_adaptive(resume=True) continues it
+            dev = self.dscene.device
+            if ad['stats'].dtype != np.float32 or ad['stats'].shape != acc.shape[:2] + (4,):
+                raise ValueError(f'checkpoint stats have shape {ad["stats"].shape} / {ad["stats"].dtype}')
+            self.stats = torch.from_numpy(ad['stats']).to(dev)
+            ids = np.flatnonzero(ad['tile_state']).astype(np.int32)
+            lst = np.zeros(ad['tile_state'].size, np.int32)
+            lst[:ids.size] = ids
+            self._resume_state['adaptive'] = ad['adaptive']
+            self._resume_tiles = {'state': torch.from_numpy(ad['tile_state'].astype(np.int32)).to(dev),
+                                  'err': torch.from_numpy(ad['tile_err'].astype(np.float32)).to(dev),
+                                  'list': torch.from_numpy(lst).to(dev), 'n': int(ids.size)}
+            self.adaptive_passes = [{'pass': i, 'active_tiles': int(r[0]), 'samples': int(r[1]), 'traced': int(r[2]),
+                                     'seconds': float(sec), 'active_after': int(r[3])}
+                                    for i, (r, sec) in enumerate(zip(ad['adaptive_passes'], ad['adaptive_seconds']))]
 
     def _check_resume_state(self):
         cur = self._render_state()
@@ -238,9 +378,20 @@ class MI355XRenderer:
                 raise ValueError(f'checkpoint was written for another render: {k} differs')
         if tuple(self.accum.shape) != (int(cur['height']), int(cur['width']), 3):
             raise ValueError('checkpoint accumulator does not match the image size')
+        if self._is_adaptive():  # the adaptive parameters and the tile grid must match too
+            a = self._adaptive
+            want = np.array([a['target_error'], a['pass_spp'], a['min_spp'], a['max_spp']], np.float64)
+            if not np.array_equal(want, self._resume_state.get('adaptive')):
+                raise ValueError('checkpoint was written for another render: adaptive differs')
+            _, _, tx, ty = self.integrator.tile_grid(self.frame)
+            if self._resume_tiles['state'].numel() != tx * ty:
+                raise ValueError('checkpoint was written for another render: tile grid differs')
+            self._tiles = dict(self._resume_tiles, grid=(tx, ty))
 
     # ----------------------------------------------------------------- output
     def image_u8(self, sample_count=None):
+        if sample_count is None and self._is_adaptive():  # each pixel by its own sample count
+            return self.integrator.tonemap(self.accum, stats=self.stats).cpu().numpy()
         spp = self.cam.samples_per_pixel if sample_count is None else sample_count
         return self.integrator.tonemap(self.accum, spp).cpu().numpy()
 
@@ -313,6 +464,17 @@ class MI355XRenderer:
             print(f'Segments/sample: {c["segments"] / c["paths"]:.3f} | '
                   f'medium traversals/sample: {c["medium"] / c["paths"]:.3f}')
         self._print_depth_stats()
+        if self._is_adaptive() and self.adaptive_passes and self._adaptive is not None:
+            px = self.cam.img_width * self.cam.img_height
+            uniform = px * self._adaptive['max_spp']
+            print('\nAdaptive passes (active tiles | samples traced | share of a uniform '
+                  f'{self._adaptive["max_spp"]}-spp render):')
+            total = 0
+            for q in self.adaptive_passes:
+                total += q['traced']
+                print(f'  pass {q["pass"] + 1:3d}: {q["active_tiles"]:7d} | {q["traced"]:13,} | '
+                      f'{100.0 * q["traced"] / uniform:6.2f}%')
+            print(f'  total: {total:,} of {uniform:,} samples ({100.0 * total / uniform:.1f}%)')
 
     _print_stats = print_statistics
 
