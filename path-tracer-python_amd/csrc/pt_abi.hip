@@ -4,6 +4,11 @@
 // happens inside a render call; the megakernel calls are asynchronous and
 // graph-capturable, the wavefront reads its live-slot counts back every 4
 // iterations (pinned 4-byte slots, allocated once).
+// Layout: the four small kernels; conversion of scene and frame; the shared
+// argument checks; one body per pair of entry points that differ by an
+// optional argument (plain / stats render, whole-frame / listed trace, plain /
+// stats resolve, the clears, the tone maps); the extern "C" entry points.
+// Every rejected argument and every no-op returns before the first HIP call.
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
@@ -94,6 +99,7 @@ static int check_hip(hipError_t e, const char* what) {
 }
 
 static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+static bool bad16(const void* p) { return !p || !aligned16(p); }  // NULL or misaligned
 
 static int to_dev_scene(const ptmi_scene_view* s, DevScene& d) {
   if (!s) return fail(PTMI_EINVAL, "scene is NULL");
@@ -106,12 +112,12 @@ static int to_dev_scene(const ptmi_scene_view* s, DevScene& d) {
   if (np > 0 && s->n_inner != np - 1)
     return fail(PTMI_EINVAL, "binary BVH with one primitive per leaf needs n_inner = prims - 1 (%d vs %d)",
                 s->n_inner, np - 1);
-  if (s->n_inner > 0 && (!s->nodes || !aligned16(s->nodes))) return fail(PTMI_EINVAL, "nodes NULL/misaligned");
-  if (s->num_spheres > 0 && (!s->spheres || !aligned16(s->spheres))) return fail(PTMI_EINVAL, "spheres");
-  if (s->num_quads > 0 && (!s->quads || !aligned16(s->quads))) return fail(PTMI_EINVAL, "quads");
-  if (s->num_triangles > 0 && (!s->tris || !aligned16(s->tris))) return fail(PTMI_EINVAL, "tris");
-  if (np > 0 && (!s->mats || !aligned16(s->mats))) return fail(PTMI_EINVAL, "mats");
-  if (!s->perlin_vec || !aligned16(s->perlin_vec) || !s->perlin_perm) return fail(PTMI_EINVAL, "perlin tables");
+  if (s->n_inner > 0 && bad16(s->nodes)) return fail(PTMI_EINVAL, "nodes NULL/misaligned");
+  if (s->num_spheres > 0 && bad16(s->spheres)) return fail(PTMI_EINVAL, "spheres");
+  if (s->num_quads > 0 && bad16(s->quads)) return fail(PTMI_EINVAL, "quads");
+  if (s->num_triangles > 0 && bad16(s->tris)) return fail(PTMI_EINVAL, "tris");
+  if (np > 0 && bad16(s->mats)) return fail(PTMI_EINVAL, "mats");
+  if (bad16(s->perlin_vec) || !s->perlin_perm) return fail(PTMI_EINVAL, "perlin tables");
   if (s->num_images < 0 || s->num_images > PTMI_MAX_IMAGES) return fail(PTMI_EINVAL, "num_images");
   if (s->num_images > 0 && !s->texels) return fail(PTMI_EINVAL, "texels");
   // The reference's 64-slot stack never overflows for leaf depth <= 62
@@ -204,6 +210,145 @@ static int check_traversal(const DevScene& sc, const DevFrame& fr) {
   return PTMI_OK;
 }
 
+// ---------------------------------------------------------------- shared checks
+static bool aligned4(const void* p) { return ((uintptr_t)p & 3u) == 0; }
+
+// The prologue of every call that takes a scene.
+static int to_dev(const ptmi_scene_view* scene, const ptmi_frame* frame, DevScene& sc, DevFrame& fr) {
+  if (int rc = to_dev_scene(scene, sc)) return rc;
+  if (int rc = to_dev_frame(frame, fr)) return rc;
+  return check_traversal(sc, fr);
+}
+
+static int check_accum(const float* accum) { return accum ? PTMI_OK : fail(PTMI_EINVAL, "accum is NULL"); }
+static int check_stats(const float* stats) {
+  return bad16(stats) ? fail(PTMI_EINVAL, "stats NULL/misaligned") : PTMI_OK;
+}
+
+// batch: the workspace of one whole batch (the trace / resolve halves), not of one sample.
+static int check_workspace(const void* ws, size_t bytes, size_t need, bool batch) {
+  if (!bad16(ws) && bytes >= need) return PTMI_OK;
+  return fail(PTMI_EINVAL, "workspace too small/misaligned%s (%zu < %zu)", batch ? " for one batch" : "", bytes, need);
+}
+
+static bool bad_tile_count(int32_t n_tiles, const DevFrame& fr) {
+  return n_tiles < 0 || (int64_t)n_tiles > mk_tile_count(fr);
+}
+
+// One thread per element in grid-stride loops: at most 4096 blocks.
+static dim3 capped_grid(int64_t n) {
+  const int64_t g = (n + kBlock - 1) / kBlock;
+  return dim3((unsigned)(g > 4096 ? 4096 : g));
+}
+
+// ------------------------------- one body per group of entry points (`what` names the public one)
+// Each keeps one order: scene, frame, traversal, the call's own arguments as
+// declared, then the no-op returns around the workspace check.
+enum RenderKind { kMkStaged, kWf, kWfStats };  // ptmi_mk_render_ws, ptmi_wf_render, ptmi_wf_render_stats
+
+static int render_ws_any(const char* what, RenderKind kind, const ptmi_scene_view* scene, const ptmi_frame* frame,
+                         void* ws, size_t ws_bytes, float* accum, float* stats, int32_t s_begin, int32_t s_count,
+                         uint64_t* counters, void* stream) {
+  DevScene sc;
+  DevFrame fr;
+  if (int rc = to_dev(scene, frame, sc, fr)) return rc;
+  if (int rc = check_accum(accum)) return rc;
+  if (kind == kWfStats)
+    if (int rc = check_stats(stats)) return rc;
+  if (s_begin < 0 || s_count < 0) return fail(PTMI_EINVAL, "bad sample range");
+  const int32_t npix = fr.w * fr.n_rows;
+  if (npix == 0) return PTMI_OK;
+  const size_t need = kind == kMkStaged ? mk_workspace_bytes(npix, 1) : wf_workspace_bytes(npix, 1);
+  if (int rc = check_workspace(ws, ws_bytes, need, false)) return rc;
+  if (s_count == 0) return PTMI_OK;
+  unsigned long long* cnt = (unsigned long long*)counters;
+  const hipStream_t st = (hipStream_t)stream;
+  const int32_t slots = stack_needed(scene);
+  return check_hip(kind == kMkStaged ? mk_render_staged(sc, fr, slots, ws, ws_bytes, accum, s_begin, s_count, cnt, st)
+                                     : wf_render(sc, fr, slots, ws, ws_bytes, accum, s_begin, s_count, cnt, st, stats),
+                   what);
+}
+
+// ptmi_mk_trace_ws / ptmi_mk_trace_tiles_ws (listed: the call has a tile list).
+static int mk_trace_any(const char* what, bool listed, const ptmi_scene_view* scene, const ptmi_frame* frame, void* ws,
+                        size_t ws_bytes, const int32_t* tile_list, int32_t n_tiles, int32_t s_begin, int32_t s_count,
+                        uint64_t* counters, void* stream) {
+  DevScene sc;
+  DevFrame fr;
+  if (int rc = to_dev(scene, frame, sc, fr)) return rc;
+  if (s_begin < 0 || s_count < 1) return fail(PTMI_EINVAL, "bad sample range");
+  if (listed && bad_tile_count(n_tiles, fr))
+    return fail(PTMI_EINVAL, "n_tiles %d outside [0, %lld]", n_tiles, (long long)mk_tile_count(fr));
+  if (listed && n_tiles > 0 && (!tile_list || !aligned4(tile_list)))
+    return fail(PTMI_EINVAL, "tile_list NULL/misaligned");
+  const int32_t npix = fr.w * fr.n_rows;
+  if (npix == 0) return PTMI_OK;
+  if ((int64_t)s_count > mk_max_batch(fr))
+    return fail(PTMI_ECAPACITY, "%d samples exceed one batch's 2^32 item ids", s_count);
+  if (int rc = check_workspace(ws, ws_bytes, mk_workspace_bytes(npix, s_count), true)) return rc;
+  if (listed && n_tiles == 0) return PTMI_OK;
+  return check_hip(mk_trace_staged(sc, fr, stack_needed(scene), ws, tile_list, n_tiles, s_begin, s_count,
+                                   (unsigned long long*)counters, (hipStream_t)stream),
+                   what);
+}
+
+// ptmi_mk_resolve_ws / ptmi_mk_resolve_stats_ws (with_stats: the call has stats and an optional tile list).
+static int mk_resolve_any(const char* what, bool with_stats, const ptmi_frame* frame, const void* ws, size_t ws_bytes,
+                          float* accum, float* stats, const int32_t* tile_list, int32_t n_tiles, int32_t s_count,
+                          void* stream) {
+  DevFrame fr;
+  if (int rc = to_dev_frame(frame, fr)) return rc;
+  if (int rc = check_accum(accum)) return rc;
+  if (with_stats)
+    if (int rc = check_stats(stats)) return rc;
+  if (s_count < 1) return fail(PTMI_EINVAL, "sample_count must be >= 1");
+  if (tile_list && (!aligned4(tile_list) || bad_tile_count(n_tiles, fr)))
+    return fail(PTMI_EINVAL, "tile_list misaligned or n_tiles %d outside [0, %lld]", n_tiles,
+                (long long)mk_tile_count(fr));
+  const int32_t npix = fr.w * fr.n_rows;
+  if (npix == 0) return PTMI_OK;
+  if (int rc = check_workspace(ws, ws_bytes, mk_workspace_bytes(npix, s_count), true)) return rc;
+  if (tile_list && n_tiles == 0) return PTMI_OK;
+  const float* staging = (const float*)ws;
+  const hipStream_t st = (hipStream_t)stream;
+  return check_hip(with_stats ? launch_stats_resolve(fr, staging, npix, s_count, accum, stats, tile_list, n_tiles,
+                                                     kProfMkResolve, st)
+                              : launch_stage_resolve(fr, staging, npix, s_count, accum, kProfMkResolve, st),
+                   what);
+}
+
+// ptmi_clear (buf = accum) / ptmi_stats_clear (buf = stats).
+static int clear_any(bool is_stats, const ptmi_frame* frame, float* buf, void* stream) {
+  DevFrame fr;
+  if (int rc = to_dev_frame(frame, fr)) return rc;
+  if (int rc = is_stats ? check_stats(buf) : check_accum(buf)) return rc;
+  const int32_t npix = fr.w * fr.n_rows;
+  if (npix == 0) return PTMI_OK;
+  if (is_stats)
+    hipLaunchKernelGGL(stats_clear_kernel, capped_grid(npix), dim3(kBlock), 0, (hipStream_t)stream, fr, (float4*)buf);
+  else
+    hipLaunchKernelGGL(clear_kernel, capped_grid(npix), dim3(kBlock), 0, (hipStream_t)stream, fr, buf);
+  return check_hip(hipGetLastError(), is_stats ? "stats clear launch" : "clear launch");
+}
+
+// ptmi_tonemap (one spp for the image) / ptmi_tonemap_stats (with_stats: each pixel's own count).
+static int tonemap_any(bool with_stats, const float* accum, const float* stats, uint8_t* out, int32_t width,
+                       int32_t height, int32_t spp, void* stream) {
+  if (!accum || !out || width <= 0 || height <= 0) return fail(PTMI_EINVAL, "bad tonemap arguments");
+  if (with_stats)
+    if (int rc = check_stats(stats)) return rc;
+  const int64_t n = (int64_t)width * height * 3;
+  if (n > 0x7fffffff) return fail(PTMI_ECAPACITY, "image too large");
+  const float scale = (float)(1.0 / (double)(spp > 1 ? spp : 1));  // python float -> f32 (NEP 50)
+  if (with_stats)
+    hipLaunchKernelGGL(tonemap_stats_kernel, capped_grid(n), dim3(kBlock), 0, (hipStream_t)stream, accum,
+                       (const float4*)stats, out, (int32_t)n);
+  else
+    hipLaunchKernelGGL(tonemap_kernel, capped_grid(n), dim3(kBlock), 0, (hipStream_t)stream, accum, out, (int32_t)n,
+                       scale);
+  return check_hip(hipGetLastError(), with_stats ? "tonemap_stats launch" : "tonemap launch");
+}
+
 extern "C" {
 
 int ptmi_version(void) { return PTMI_ABI_VERSION; }
@@ -221,11 +366,8 @@ int ptmi_mk_render(const ptmi_scene_view* scene, const ptmi_frame* frame, float*
                    int32_t sample_count, uint64_t* counters, void* stream) {
   DevScene sc;
   DevFrame fr;
-  int rc = to_dev_scene(scene, sc);
-  if (rc) return rc;
-  if ((rc = to_dev_frame(frame, fr))) return rc;
-  if ((rc = check_traversal(sc, fr))) return rc;
-  if (!accum) return fail(PTMI_EINVAL, "accum is NULL");
+  if (int rc = to_dev(scene, frame, sc, fr)) return rc;
+  if (int rc = check_accum(accum)) return rc;
   if (sample_begin < 0 || sample_count < 0) return fail(PTMI_EINVAL, "bad sample range");
   if (sample_count == 0 || fr.n_rows == 0) return PTMI_OK;
   return check_hip(mk_render(sc, fr, stack_needed(scene), accum, sample_begin, sample_count,
@@ -246,44 +388,14 @@ size_t ptmi_mk_workspace_bytes(const ptmi_frame* frame, int32_t batch_samples) {
 int ptmi_mk_render_ws(const ptmi_scene_view* scene, const ptmi_frame* frame, void* workspace,
                       size_t workspace_bytes, float* accum, int32_t sample_begin, int32_t sample_count,
                       uint64_t* counters, void* stream) {
-  DevScene sc;
-  DevFrame fr;
-  int rc = to_dev_scene(scene, sc);
-  if (rc) return rc;
-  if ((rc = to_dev_frame(frame, fr))) return rc;
-  if ((rc = check_traversal(sc, fr))) return rc;
-  if (!accum) return fail(PTMI_EINVAL, "accum is NULL");
-  if (sample_begin < 0 || sample_count < 0) return fail(PTMI_EINVAL, "bad sample range");
-  const int32_t npix = fr.w * fr.n_rows;
-  if (npix == 0) return PTMI_OK;
-  if (!workspace || !aligned16(workspace) || workspace_bytes < mk_workspace_bytes(npix, 1))
-    return fail(PTMI_EINVAL, "workspace too small/misaligned (%zu < %zu)", workspace_bytes,
-                mk_workspace_bytes(npix, 1));
-  if (sample_count == 0) return PTMI_OK;
-  return check_hip(mk_render_staged(sc, fr, stack_needed(scene), workspace, workspace_bytes, accum, sample_begin,
-                                    sample_count, (unsigned long long*)counters, (hipStream_t)stream),
-                   "mk_render_ws");
+  return render_ws_any("mk_render_ws", kMkStaged, scene, frame, workspace, workspace_bytes, accum, nullptr,
+                       sample_begin, sample_count, counters, stream);
 }
 
 int ptmi_mk_trace_ws(const ptmi_scene_view* scene, const ptmi_frame* frame, void* workspace, size_t workspace_bytes,
                      int32_t sample_begin, int32_t sample_count, uint64_t* counters, void* stream) {
-  DevScene sc;
-  DevFrame fr;
-  int rc = to_dev_scene(scene, sc);
-  if (rc) return rc;
-  if ((rc = to_dev_frame(frame, fr))) return rc;
-  if ((rc = check_traversal(sc, fr))) return rc;
-  if (sample_begin < 0 || sample_count < 1) return fail(PTMI_EINVAL, "bad sample range");
-  const int32_t npix = fr.w * fr.n_rows;
-  if (npix == 0) return PTMI_OK;
-  if ((int64_t)sample_count > mk_max_batch(fr))
-    return fail(PTMI_ECAPACITY, "%d samples exceed one batch's 2^32 item ids", sample_count);
-  const size_t need = mk_workspace_bytes(npix, sample_count);
-  if (!workspace || !aligned16(workspace) || workspace_bytes < need)
-    return fail(PTMI_EINVAL, "workspace too small/misaligned for one batch (%zu < %zu)", workspace_bytes, need);
-  return check_hip(mk_trace_staged(sc, fr, stack_needed(scene), workspace, sample_begin, sample_count,
-                                   (unsigned long long*)counters, (hipStream_t)stream),
-                   "mk_trace_ws");
+  return mk_trace_any("mk_trace_ws", false, scene, frame, workspace, workspace_bytes, nullptr, 0, sample_begin,
+                      sample_count, counters, stream);
 }
 
 int64_t ptmi_mk_max_batch(const ptmi_frame* frame) {
@@ -294,19 +406,8 @@ int64_t ptmi_mk_max_batch(const ptmi_frame* frame) {
 
 int ptmi_mk_resolve_ws(const ptmi_frame* frame, const void* workspace, size_t workspace_bytes, float* accum,
                        int32_t sample_count, void* stream) {
-  DevFrame fr;
-  int rc = to_dev_frame(frame, fr);
-  if (rc) return rc;
-  if (!accum) return fail(PTMI_EINVAL, "accum is NULL");
-  if (sample_count < 1) return fail(PTMI_EINVAL, "sample_count must be >= 1");
-  const int32_t npix = fr.w * fr.n_rows;
-  if (npix == 0) return PTMI_OK;
-  const size_t need = mk_workspace_bytes(npix, sample_count);
-  if (!workspace || !aligned16(workspace) || workspace_bytes < need)
-    return fail(PTMI_EINVAL, "workspace too small/misaligned for one batch (%zu < %zu)", workspace_bytes, need);
-  return check_hip(launch_stage_resolve(fr, (const float*)workspace, npix, sample_count, accum, kProfMkResolve,
-                                        (hipStream_t)stream),
-                   "mk_resolve_ws");
+  return mk_resolve_any("mk_resolve_ws", false, frame, workspace, workspace_bytes, accum, nullptr, nullptr, 0,
+                        sample_count, stream);
 }
 
 size_t ptmi_wf_workspace_bytes(const ptmi_frame* frame, int32_t batch_samples) {
@@ -325,23 +426,8 @@ size_t ptmi_wf_workspace_bytes(const ptmi_frame* frame, int32_t batch_samples) {
 
 int ptmi_wf_render(const ptmi_scene_view* scene, const ptmi_frame* frame, void* workspace, size_t workspace_bytes,
                    float* accum, int32_t sample_begin, int32_t sample_count, uint64_t* counters, void* stream) {
-  DevScene sc;
-  DevFrame fr;
-  int rc = to_dev_scene(scene, sc);
-  if (rc) return rc;
-  if ((rc = to_dev_frame(frame, fr))) return rc;
-  if ((rc = check_traversal(sc, fr))) return rc;
-  if (!accum) return fail(PTMI_EINVAL, "accum is NULL");
-  if (sample_begin < 0 || sample_count < 0) return fail(PTMI_EINVAL, "bad sample range");
-  int32_t npix = fr.w * fr.n_rows;
-  if (npix == 0) return PTMI_OK;
-  if (!workspace || !aligned16(workspace) || workspace_bytes < wf_workspace_bytes(npix, 1))
-    return fail(PTMI_EINVAL, "workspace too small/misaligned (%zu < %zu)", workspace_bytes,
-                wf_workspace_bytes(npix, 1));
-  if (sample_count == 0) return PTMI_OK;
-  return check_hip(wf_render(sc, fr, stack_needed(scene), workspace, workspace_bytes, accum, sample_begin,
-                             sample_count, (unsigned long long*)counters, (hipStream_t)stream),
-                   "wf_render");
+  return render_ws_any("wf_render", kWf, scene, frame, workspace, workspace_bytes, accum, nullptr, sample_begin,
+                       sample_count, counters, stream);
 }
 
 int ptmi_wf_set_drain_at(int32_t divisor) {
@@ -349,133 +435,51 @@ int ptmi_wf_set_drain_at(int32_t divisor) {
   return wf_set_drain_at(divisor);
 }
 
-int ptmi_clear(const ptmi_frame* frame, float* accum, void* stream) {
-  DevFrame fr;
-  int rc = to_dev_frame(frame, fr);
-  if (rc) return rc;
-  if (!accum) return fail(PTMI_EINVAL, "accum is NULL");
-  int32_t npix = fr.w * fr.n_rows;
-  if (npix == 0) return PTMI_OK;
-  unsigned g = (unsigned)((npix + kBlock - 1) / kBlock);
-  if (g > 4096) g = 4096;
-  hipLaunchKernelGGL(clear_kernel, dim3(g), dim3(kBlock), 0, (hipStream_t)stream, fr, accum);
-  return check_hip(hipGetLastError(), "clear launch");
-}
+int ptmi_clear(const ptmi_frame* frame, float* accum, void* stream) { return clear_any(false, frame, accum, stream); }
 
 int ptmi_tonemap(const float* accum, uint8_t* out, int32_t width, int32_t height, int32_t spp, void* stream) {
-  if (!accum || !out || width <= 0 || height <= 0) return fail(PTMI_EINVAL, "bad tonemap arguments");
-  int64_t n = (int64_t)width * height * 3;
-  if (n > 0x7fffffff) return fail(PTMI_ECAPACITY, "image too large");
-  float scale = (float)(1.0 / (double)(spp > 1 ? spp : 1));  // python float -> f32 (NEP 50)
-  unsigned g = (unsigned)((n + kBlock - 1) / kBlock);
-  if (g > 4096) g = 4096;
-  hipLaunchKernelGGL(tonemap_kernel, dim3(g), dim3(kBlock), 0, (hipStream_t)stream, accum, out, (int32_t)n, scale);
-  return check_hip(hipGetLastError(), "tonemap launch");
+  return tonemap_any(false, accum, nullptr, out, width, height, spp, stream);
 }
 
 // ------------------------------------------------------------- adaptive (ABI v8)
-static bool aligned4(const void* p) { return ((uintptr_t)p & 3u) == 0; }
-
 int ptmi_mk_tile_grid(const ptmi_frame* frame, int32_t* tile_w, int32_t* tile_h, int32_t* tiles_x, int32_t* tiles_y) {
   DevFrame fr;
-  int rc = to_dev_frame(frame, fr);
-  if (rc) return rc;
+  if (int rc = to_dev_frame(frame, fr)) return rc;
   if (!tile_w || !tile_h || !tiles_x || !tiles_y) return fail(PTMI_EINVAL, "tile grid output is NULL");
   mk_tile_grid(fr, tile_w, tile_h, tiles_x, tiles_y);
   return PTMI_OK;
 }
 
 int ptmi_stats_clear(const ptmi_frame* frame, float* stats, void* stream) {
-  DevFrame fr;
-  int rc = to_dev_frame(frame, fr);
-  if (rc) return rc;
-  if (!stats || !aligned16(stats)) return fail(PTMI_EINVAL, "stats NULL/misaligned");
-  int32_t npix = fr.w * fr.n_rows;
-  if (npix == 0) return PTMI_OK;
-  unsigned g = (unsigned)((npix + kBlock - 1) / kBlock);
-  if (g > 4096) g = 4096;
-  hipLaunchKernelGGL(stats_clear_kernel, dim3(g), dim3(kBlock), 0, (hipStream_t)stream, fr, (float4*)stats);
-  return check_hip(hipGetLastError(), "stats clear launch");
+  return clear_any(true, frame, stats, stream);
 }
 
 int ptmi_mk_trace_tiles_ws(const ptmi_scene_view* scene, const ptmi_frame* frame, void* workspace,
                            size_t workspace_bytes, const int32_t* tile_list, int32_t n_tiles, int32_t sample_begin,
                            int32_t sample_count, uint64_t* counters, void* stream) {
-  DevScene sc;
-  DevFrame fr;
-  int rc = to_dev_scene(scene, sc);
-  if (rc) return rc;
-  if ((rc = to_dev_frame(frame, fr))) return rc;
-  if ((rc = check_traversal(sc, fr))) return rc;
-  if (sample_begin < 0 || sample_count < 1) return fail(PTMI_EINVAL, "bad sample range");
-  if (n_tiles < 0 || (int64_t)n_tiles > mk_tile_count(fr))
-    return fail(PTMI_EINVAL, "n_tiles %d outside [0, %lld]", n_tiles, (long long)mk_tile_count(fr));
-  if (n_tiles > 0 && (!tile_list || !aligned4(tile_list))) return fail(PTMI_EINVAL, "tile_list NULL/misaligned");
-  const int32_t npix = fr.w * fr.n_rows;
-  if (npix == 0) return PTMI_OK;
-  if ((int64_t)sample_count > mk_max_batch(fr))
-    return fail(PTMI_ECAPACITY, "%d samples exceed one batch's 2^32 item ids", sample_count);
-  const size_t need = mk_workspace_bytes(npix, sample_count);
-  if (!workspace || !aligned16(workspace) || workspace_bytes < need)
-    return fail(PTMI_EINVAL, "workspace too small/misaligned for one batch (%zu < %zu)", workspace_bytes, need);
-  if (n_tiles == 0) return PTMI_OK;
-  return check_hip(mk_trace_staged_tiles(sc, fr, stack_needed(scene), workspace, tile_list, n_tiles, sample_begin,
-                                         sample_count, (unsigned long long*)counters, (hipStream_t)stream),
-                   "mk_trace_tiles_ws");
+  return mk_trace_any("mk_trace_tiles_ws", true, scene, frame, workspace, workspace_bytes, tile_list, n_tiles,
+                      sample_begin, sample_count, counters, stream);
 }
 
 int ptmi_mk_resolve_stats_ws(const ptmi_frame* frame, const void* workspace, size_t workspace_bytes, float* accum,
                              float* stats, const int32_t* tile_list, int32_t n_tiles, int32_t sample_count,
                              void* stream) {
-  DevFrame fr;
-  int rc = to_dev_frame(frame, fr);
-  if (rc) return rc;
-  if (!accum) return fail(PTMI_EINVAL, "accum is NULL");
-  if (!stats || !aligned16(stats)) return fail(PTMI_EINVAL, "stats NULL/misaligned");
-  if (sample_count < 1) return fail(PTMI_EINVAL, "sample_count must be >= 1");
-  if (tile_list && (!aligned4(tile_list) || n_tiles < 0 || (int64_t)n_tiles > mk_tile_count(fr)))
-    return fail(PTMI_EINVAL, "tile_list misaligned or n_tiles %d outside [0, %lld]", n_tiles,
-                (long long)mk_tile_count(fr));
-  const int32_t npix = fr.w * fr.n_rows;
-  if (npix == 0) return PTMI_OK;
-  const size_t need = mk_workspace_bytes(npix, sample_count);
-  if (!workspace || !aligned16(workspace) || workspace_bytes < need)
-    return fail(PTMI_EINVAL, "workspace too small/misaligned for one batch (%zu < %zu)", workspace_bytes, need);
-  if (tile_list && n_tiles == 0) return PTMI_OK;
-  return check_hip(launch_stats_resolve(fr, (const float*)workspace, npix, sample_count, accum, stats, tile_list,
-                                        n_tiles, kProfMkResolve, (hipStream_t)stream),
-                   "mk_resolve_stats_ws");
+  return mk_resolve_any("mk_resolve_stats_ws", true, frame, workspace, workspace_bytes, accum, stats, tile_list,
+                        n_tiles, sample_count, stream);
 }
 
 int ptmi_wf_render_stats(const ptmi_scene_view* scene, const ptmi_frame* frame, void* workspace,
                          size_t workspace_bytes, float* accum, float* stats, int32_t sample_begin,
                          int32_t sample_count, uint64_t* counters, void* stream) {
-  DevScene sc;
-  DevFrame fr;
-  int rc = to_dev_scene(scene, sc);
-  if (rc) return rc;
-  if ((rc = to_dev_frame(frame, fr))) return rc;
-  if ((rc = check_traversal(sc, fr))) return rc;
-  if (!accum) return fail(PTMI_EINVAL, "accum is NULL");
-  if (!stats || !aligned16(stats)) return fail(PTMI_EINVAL, "stats NULL/misaligned");
-  if (sample_begin < 0 || sample_count < 0) return fail(PTMI_EINVAL, "bad sample range");
-  int32_t npix = fr.w * fr.n_rows;
-  if (npix == 0) return PTMI_OK;
-  if (!workspace || !aligned16(workspace) || workspace_bytes < wf_workspace_bytes(npix, 1))
-    return fail(PTMI_EINVAL, "workspace too small/misaligned (%zu < %zu)", workspace_bytes,
-                wf_workspace_bytes(npix, 1));
-  if (sample_count == 0) return PTMI_OK;
-  return check_hip(wf_render(sc, fr, stack_needed(scene), workspace, workspace_bytes, accum, sample_begin,
-                             sample_count, (unsigned long long*)counters, (hipStream_t)stream, stats),
-                   "wf_render_stats");
+  return render_ws_any("wf_render_stats", kWfStats, scene, frame, workspace, workspace_bytes, accum, stats,
+                       sample_begin, sample_count, counters, stream);
 }
 
 int ptmi_tile_update(const ptmi_frame* frame, const float* stats, float threshold, int32_t min_spp, int32_t max_spp,
                      int32_t* tile_state, float* tile_err, int32_t* tile_list, int32_t* n_active, void* stream) {
   DevFrame fr;
-  int rc = to_dev_frame(frame, fr);
-  if (rc) return rc;
-  if (!stats || !aligned16(stats)) return fail(PTMI_EINVAL, "stats NULL/misaligned");
+  if (int rc = to_dev_frame(frame, fr)) return rc;
+  if (int rc = check_stats(stats)) return rc;
   if (!(threshold >= 0.0f)) return fail(PTMI_EINVAL, "threshold must be >= 0");
   if (min_spp < 0 || max_spp < min_spp) return fail(PTMI_EINVAL, "bad spp range [%d, %d]", min_spp, max_spp);
   if (!tile_state || !tile_err || !tile_list || !n_active || !aligned4(tile_state) || !aligned4(tile_err) ||
@@ -488,15 +492,7 @@ int ptmi_tile_update(const ptmi_frame* frame, const float* stats, float threshol
 
 int ptmi_tonemap_stats(const float* accum, const float* stats, uint8_t* out, int32_t width, int32_t height,
                        void* stream) {
-  if (!accum || !out || width <= 0 || height <= 0) return fail(PTMI_EINVAL, "bad tonemap arguments");
-  if (!stats || !aligned16(stats)) return fail(PTMI_EINVAL, "stats NULL/misaligned");
-  int64_t n = (int64_t)width * height * 3;
-  if (n > 0x7fffffff) return fail(PTMI_ECAPACITY, "image too large");
-  unsigned g = (unsigned)((n + kBlock - 1) / kBlock);
-  if (g > 4096) g = 4096;
-  hipLaunchKernelGGL(tonemap_stats_kernel, dim3(g), dim3(kBlock), 0, (hipStream_t)stream, accum,
-                     (const float4*)stats, out, (int32_t)n);
-  return check_hip(hipGetLastError(), "tonemap_stats launch");
+  return tonemap_any(true, accum, stats, out, width, height, 0, stream);
 }
 
 int ptmi_prof_start(int32_t max_launches) {

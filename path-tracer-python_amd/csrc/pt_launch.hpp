@@ -6,9 +6,38 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "pt_device.hpp"
 
 namespace ptmi {
+// The one traversal dispatch of the library: (frame.traversal, stack slots
+// needed = max_leaf_depth + 1) to a kernel's compile-time (STACK, TRAV),
+// handed to f as two std::integral_constant<int, .> arguments. Stackless
+// first; else the smallest stack rung that holds stack_needed; else, for leaf
+// depth > 62, the reference's own 64-entry walk, whose stack drops pushes
+// (TravRS, pt_device.hpp). FINE adds the exact 17-, 18- and 19-slot rungs
+// (the staged megakernel); the direct megakernel and the wavefront use the
+// coarse set and instantiate no kernel for those three.
+template <bool FINE, class F>
+hipError_t dispatch_traversal(const DevFrame& fr, int32_t stack_needed, F&& f) {
+  using std::integral_constant;
+  constexpr integral_constant<int, PTMI_TRAV_STACK> stack{};
+  if (fr.traversal == PTMI_TRAV_STACKLESS)
+    return f(integral_constant<int, 1>{}, integral_constant<int, PTMI_TRAV_STACKLESS>{});
+  if (stack_needed <= 16) return f(integral_constant<int, 16>{}, stack);
+  if constexpr (FINE) {
+    if (stack_needed == 17) return f(integral_constant<int, 17>{}, stack);
+    if (stack_needed == 18) return f(integral_constant<int, 18>{}, stack);
+    if (stack_needed == 19) return f(integral_constant<int, 19>{}, stack);
+  }
+  if (stack_needed <= 20) return f(integral_constant<int, 20>{}, stack);
+  if (stack_needed <= 24) return f(integral_constant<int, 24>{}, stack);
+  if (stack_needed <= 32) return f(integral_constant<int, 32>{}, stack);
+  if (stack_needed <= kRefStackSlots - 1) return f(integral_constant<int, 64>{}, stack);
+  return f(integral_constant<int, kRefStackSlots>{}, integral_constant<int, kTravRefStack>{});
+}
+
 // Megakernel, accumulating in registers straight into accum (one work unit
 // per 16x16 tile for all samples of the call).
 hipError_t mk_render(const DevScene& sc, const DevFrame& fr, int32_t stack_needed, float* accum,
@@ -20,10 +49,13 @@ hipError_t mk_render_staged(const DevScene& sc, const DevFrame& fr, int32_t stac
                             size_t ws_bytes, float* accum, int32_t s_begin, int32_t s_count,
                             unsigned long long* counters, hipStream_t stream);
 // The two halves of one staged batch, for callers that schedule them
-// themselves (ptmi_mk_trace_ws / ptmi_mk_resolve_ws): the megakernel into the
-// workspace's staging, and the in-order resolve into accum.
+// themselves (ptmi_mk_trace_ws / ptmi_mk_trace_tiles_ws, ptmi_mk_resolve_ws):
+// the megakernel into the workspace's staging, and the in-order resolve into
+// accum. tile_list == nullptr: the whole frame, else the tiles of
+// tile_list[0 .. n) only (device ids, ids outside the grid ignored).
 hipError_t mk_trace_staged(const DevScene& sc, const DevFrame& fr, int32_t stack_needed, void* ws,
-                           int32_t s_begin, int32_t nb, unsigned long long* counters, hipStream_t stream);
+                           const int32_t* tile_list, int32_t n, int32_t s_begin, int32_t nb,
+                           unsigned long long* counters, hipStream_t stream);
 int64_t mk_max_batch(const DevFrame& fr);
 // stats != nullptr: every batch resolves through launch_stats_resolve.
 hipError_t wf_render(const DevScene& sc, const DevFrame& fr, int32_t stack_needed, void* ws, size_t ws_bytes,
@@ -40,10 +72,6 @@ hipError_t launch_stage_resolve(const DevFrame& fr, const float* staging, int32_
 // The staged megakernel's 64-pixel tiles of a frame: tile size and grid.
 void mk_tile_grid(const DevFrame& fr, int32_t* tile_w, int32_t* tile_h, int32_t* tiles_x, int32_t* tiles_y);
 int64_t mk_tile_count(const DevFrame& fr);
-// mk_trace_staged for the tiles of tile_list[0 .. n) only (device ids, ids outside the grid ignored).
-hipError_t mk_trace_staged_tiles(const DevScene& sc, const DevFrame& fr, int32_t stack_needed, void* ws,
-                                 const int32_t* tile_list, int32_t n, int32_t s_begin, int32_t nb,
-                                 unsigned long long* counters, hipStream_t stream);
 // launch_stage_resolve plus the Welford update of stats[pixel] = {n, mean, M2, 0};
 // tile_list == nullptr: every pixel of the frame, else the pixels of the listed tiles.
 hipError_t launch_stats_resolve(const DevFrame& fr, const float* staging, int32_t npix, int32_t batch, float* accum,

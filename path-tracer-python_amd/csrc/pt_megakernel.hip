@@ -757,22 +757,13 @@ static hipError_t launch_mk(const DevScene& sc, const DevFrame& fr, float* accum
 
 hipError_t mk_render(const DevScene& sc, const DevFrame& fr, int32_t stack_needed, float* accum,
                      int32_t s_begin, int32_t s_count, unsigned long long* counters, hipStream_t stream) {
-  if (fr.traversal == PTMI_TRAV_STACKLESS)
-    return launch_mk<1, PTMI_TRAV_STACKLESS>(sc, fr, accum, s_begin, s_count, counters, stream);
-  if (stack_needed <= 16) return launch_mk<16>(sc, fr, accum, s_begin, s_count, counters, stream);
-  if (stack_needed <= 20) return launch_mk<20>(sc, fr, accum, s_begin, s_count, counters, stream);
-  if (stack_needed <= 24) return launch_mk<24>(sc, fr, accum, s_begin, s_count, counters, stream);
-  if (stack_needed <= 32) return launch_mk<32>(sc, fr, accum, s_begin, s_count, counters, stream);
-  if (stack_needed <= kRefStackSlots - 1) return launch_mk<64>(sc, fr, accum, s_begin, s_count, counters, stream);
-  // leaf depth > 62: the reference's 64-entry stack drops pushes (TravRS)
-  return launch_mk<kRefStackSlots, kTravRefStack>(sc, fr, accum, s_begin, s_count, counters, stream);
+  return dispatch_traversal<false>(fr, stack_needed, [&](auto stack, auto trav) {
+    constexpr int S = decltype(stack)::value, T = decltype(trav)::value;
+    return launch_mk<S, T>(sc, fr, accum, s_begin, s_count, counters, stream);
+  });
 }
 
 // ---------------------------------------------------------------- staged
-#ifndef PTMI_MK_STAGED_MIN_STACK
-#define PTMI_MK_STAGED_MIN_STACK 16  // staged: STACK 16 scenes use the 16-slot kernel at 5 waves/SIMD (PTMI_MK_MIN_WAVES_16)
-#endif
-
 static size_t mk_staging_bytes(int32_t npix, int32_t batch) {
   return (3 * sizeof(float) * (size_t)npix * (size_t)batch + 255) & ~(size_t)255;
 }
@@ -790,7 +781,7 @@ size_t mk_workspace_bytes(int32_t npix, int32_t batch) {  // staging + the shard
 template <int STACK, int TRAV = PTMI_TRAV_STACK, bool LISTED = false>
 static hipError_t launch_mk_trace(const DevScene& sc, const DevFrame& fr, float* staging, int32_t s_begin,
                                   int32_t nb, unsigned long long* counters, hipStream_t stream,
-                                  const int32_t* tile_list = nullptr, int32_t n_list = 0) {
+                                  const int32_t* tile_list, int32_t n_list) {
   float* accum = nullptr;  // staged kernels write staging only
   int32_t tx = 0;
   const int64_t frame_tiles = mk_tiles(fr, &tx);
@@ -834,12 +825,8 @@ static hipError_t launch_mk_trace(const DevScene& sc, const DevFrame& fr, float*
   const int64_t tail = batch_samples < PTMI_MK_SMALL_BATCH ? PTMI_MK_TAIL_DIV_SMALL : PTMI_MK_TAIL_DIV;
   const int64_t tdiv = tail * waves / kMkShards;
   wk.tail_div = (int32_t)(tdiv > 1 ? tdiv : 1);
-  if (LISTED) {  // new code checks the memset; the unlisted path keeps its behaviour
-    e0 = hipMemsetAsync(wk.ctl, 0, 256 * kMkShards, stream);
-    if (e0 != hipSuccess) return e0;
-  } else {
-    (void)hipMemsetAsync(wk.ctl, 0, 256 * kMkShards, stream);
-  }
+  e0 = hipMemsetAsync(wk.ctl, 0, 256 * kMkShards, stream);
+  if (e0 != hipSuccess) return e0;  // never launch on stale work counters
   const int pslot = prof_begin(kProfMk, stream);
   hipLaunchKernelGGL((mk_render_kernel<STACK, true, TRAV, LISTED>), dim3((unsigned)waves), dim3(kMkBlock), 0, stream,
                      sc, fr, accum, s_begin, nb, nb, staging, counters, wk);
@@ -847,40 +834,22 @@ static hipError_t launch_mk_trace(const DevScene& sc, const DevFrame& fr, float*
   return hipGetLastError();
 }
 
+// The staged megakernel takes the fine rungs: a scene that needs 16 slots or
+// fewer runs the 16-slot kernel at 5 waves/SIMD (PTMI_MK_MIN_WAVES_16).
 hipError_t mk_trace_staged(const DevScene& sc, const DevFrame& fr, int32_t stack_needed, void* ws,
-                           int32_t s_begin, int32_t nb, unsigned long long* counters, hipStream_t stream) {
-  float* st = (float*)ws;
-  if (fr.traversal == PTMI_TRAV_STACKLESS)
-    return launch_mk_trace<1, PTMI_TRAV_STACKLESS>(sc, fr, st, s_begin, nb, counters, stream);
-  if (stack_needed <= PTMI_MK_STAGED_MIN_STACK) return launch_mk_trace<16>(sc, fr, st, s_begin, nb, counters, stream);
-  if (stack_needed == 17) return launch_mk_trace<17>(sc, fr, st, s_begin, nb, counters, stream);
-  if (stack_needed == 18) return launch_mk_trace<18>(sc, fr, st, s_begin, nb, counters, stream);
-  if (stack_needed == 19) return launch_mk_trace<19>(sc, fr, st, s_begin, nb, counters, stream);
-  if (stack_needed <= 20) return launch_mk_trace<20>(sc, fr, st, s_begin, nb, counters, stream);
-  if (stack_needed <= 24) return launch_mk_trace<24>(sc, fr, st, s_begin, nb, counters, stream);
-  if (stack_needed <= 32) return launch_mk_trace<32>(sc, fr, st, s_begin, nb, counters, stream);
-  if (stack_needed <= kRefStackSlots - 1) return launch_mk_trace<64>(sc, fr, st, s_begin, nb, counters, stream);
-  // leaf depth > 62: the reference's 64-entry stack drops pushes (TravRS)
-  return launch_mk_trace<kRefStackSlots, kTravRefStack>(sc, fr, st, s_begin, nb, counters, stream);
-}
-
-hipError_t mk_trace_staged_tiles(const DevScene& sc, const DevFrame& fr, int32_t stack_needed, void* ws,
-                                 const int32_t* tl, int32_t n, int32_t s_begin, int32_t nb,
-                                 unsigned long long* counters, hipStream_t stream) {
-  float* st = (float*)ws;
-  if (fr.traversal == PTMI_TRAV_STACKLESS)
-    return launch_mk_trace<1, PTMI_TRAV_STACKLESS, true>(sc, fr, st, s_begin, nb, counters, stream, tl, n);
-  if (stack_needed <= PTMI_MK_STAGED_MIN_STACK)
-    return launch_mk_trace<16, PTMI_TRAV_STACK, true>(sc, fr, st, s_begin, nb, counters, stream, tl, n);
-  if (stack_needed == 17) return launch_mk_trace<17, PTMI_TRAV_STACK, true>(sc, fr, st, s_begin, nb, counters, stream, tl, n);
-  if (stack_needed == 18) return launch_mk_trace<18, PTMI_TRAV_STACK, true>(sc, fr, st, s_begin, nb, counters, stream, tl, n);
-  if (stack_needed == 19) return launch_mk_trace<19, PTMI_TRAV_STACK, true>(sc, fr, st, s_begin, nb, counters, stream, tl, n);
-  if (stack_needed <= 20) return launch_mk_trace<20, PTMI_TRAV_STACK, true>(sc, fr, st, s_begin, nb, counters, stream, tl, n);
-  if (stack_needed <= 24) return launch_mk_trace<24, PTMI_TRAV_STACK, true>(sc, fr, st, s_begin, nb, counters, stream, tl, n);
-  if (stack_needed <= 32) return launch_mk_trace<32, PTMI_TRAV_STACK, true>(sc, fr, st, s_begin, nb, counters, stream, tl, n);
-  if (stack_needed <= kRefStackSlots - 1)
-    return launch_mk_trace<64, PTMI_TRAV_STACK, true>(sc, fr, st, s_begin, nb, counters, stream, tl, n);
-  return launch_mk_trace<kRefStackSlots, kTravRefStack, true>(sc, fr, st, s_begin, nb, counters, stream, tl, n);
+                           const int32_t* tile_list, int32_t n, int32_t s_begin, int32_t nb,
+                           unsigned long long* counters, hipStream_t stream) {
+  // LISTED wraps the ladder rather than branching inside its callable, unlisted
+  // first: the code object then holds the unlisted kernels before the listed
+  // ones, rung by rung, as it always has.
+  auto trace = [&](auto listed) {
+    return dispatch_traversal<true>(fr, stack_needed, [&](auto stack, auto trav) {
+      return launch_mk_trace<decltype(stack)::value, decltype(trav)::value, decltype(listed)::value>(
+          sc, fr, (float*)ws, s_begin, nb, counters, stream, tile_list, n);
+    });
+  };
+  if (!tile_list) return trace(std::false_type{});
+  return trace(std::true_type{});
 }
 
 void mk_tile_grid(const DevFrame& fr, int32_t* tile_w, int32_t* tile_h, int32_t* tiles_x, int32_t* tiles_y) {
@@ -914,7 +883,7 @@ hipError_t mk_render_staged(const DevScene& sc, const DevFrame& fr, int32_t stac
   if (mk_workspace_bytes(npix, batch) > ws_bytes) return hipErrorInvalidValue;
   for (int32_t b0 = 0; b0 < s_count; b0 += batch) {
     const int32_t nb = s_count - b0 < batch ? s_count - b0 : batch;
-    hipError_t e = mk_trace_staged(sc, fr, stack_needed, ws, s_begin + b0, nb, counters, stream);
+    hipError_t e = mk_trace_staged(sc, fr, stack_needed, ws, nullptr, 0, s_begin + b0, nb, counters, stream);
     if (e == hipSuccess) e = launch_stage_resolve(fr, (const float*)ws, npix, nb, accum, kProfMkResolve, stream);
     if (e != hipSuccess) return e;
   }

@@ -1183,9 +1183,9 @@ static hipError_t wf_batch(const DevScene& sc, const DevFrame& fr, const WfBufs*
   const unsigned g = (unsigned)blocks;
   // the tail launch: one lane per continuing ray (<= capacity + the bins' padding)
   const unsigned gd = (unsigned)((wbs[0].capacity + 64 * (kBins + 1) + kWfBlock - 1) / kWfBlock);
-  {  // the stats path (ptmi_wf_render_stats) checks the memset; plain renders keep their behaviour
+  {  // never launch on stale work counters
     const hipError_t em = hipMemsetAsync(wbs[0].next, 0, kCtlWords * sizeof(int32_t), stream);
-    if (stats && em != hipSuccess) return em;
+    if (em != hipSuccess) return em;
   }
   {
     const int pslot = prof_begin(kProfWfGenerate, stream);
@@ -1392,14 +1392,10 @@ hipError_t wf_render(const DevScene& sc, const DevFrame& fr, int32_t stack_neede
       wb.by_nsq = fast_div((uint32_t)wb.nsq);
       wb.by_sqx = fast_div((uint32_t)wb.sq_x);
     }
-    hipError_t e;
-    if (fr.traversal == PTMI_TRAV_STACKLESS) e = wf_batch<1, PTMI_TRAV_STACKLESS>(sc, fr, wbs, accum, nb, counters, stream, *ps, stats);
-    else if (stack_needed <= 16) e = wf_batch<16>(sc, fr, wbs, accum, nb, counters, stream, *ps, stats);
-    else if (stack_needed <= 20) e = wf_batch<20>(sc, fr, wbs, accum, nb, counters, stream, *ps, stats);
-    else if (stack_needed <= 24) e = wf_batch<24>(sc, fr, wbs, accum, nb, counters, stream, *ps, stats);
-    else if (stack_needed <= 32) e = wf_batch<32>(sc, fr, wbs, accum, nb, counters, stream, *ps, stats);
-    else if (stack_needed <= kRefStackSlots - 1) e = wf_batch<64>(sc, fr, wbs, accum, nb, counters, stream, *ps, stats);
-    else e = wf_batch<kRefStackSlots, kTravRefStack>(sc, fr, wbs, accum, nb, counters, stream, *ps, stats);  // leaf depth > 62
+    const hipError_t e = dispatch_traversal<false>(fr, stack_needed, [&](auto stack, auto trav) {
+      constexpr int S = decltype(stack)::value, T = decltype(trav)::value;
+      return wf_batch<S, T>(sc, fr, wbs, accum, nb, counters, stream, *ps, stats);
+    });
     if (e != hipSuccess) return e;
   }
   return hipSuccess;

@@ -54,13 +54,43 @@ class Frame(C.Structure):
 TRAVERSALS = {'stack': 0, 'stackless': 1}
 
 
-EXPORTS = ('ptmi_version', 'ptmi_last_error', 'ptmi_scene_check', 'ptmi_mk_render', 'ptmi_mk_workspace_bytes',
-           'ptmi_mk_render_ws', 'ptmi_mk_trace_ws', 'ptmi_mk_max_batch', 'ptmi_mk_resolve_ws', 'ptmi_wf_workspace_bytes',
-           'ptmi_wf_render', 'ptmi_clear', 'ptmi_tonemap', 'ptmi_bvh_build_sah', 'ptmi_prof_start',
-           'ptmi_prof_stop', 'ptmi_prof_stop_busy', 'ptmi_node_bytes', 'ptmi_wf_set_drain_at',
-           # ABI v8: per-pixel error estimates and adaptive tile sampling
-           'ptmi_mk_tile_grid', 'ptmi_stats_clear', 'ptmi_mk_trace_tiles_ws', 'ptmi_mk_resolve_stats_ws',
-           'ptmi_wf_render_stats', 'ptmi_tile_update', 'ptmi_tonemap_stats')
+def _signatures():
+    """Every export of include/ptmi.h: name -> (restype, argtypes)."""
+    P, I, Z = C.c_void_p, C.c_int32, C.c_size_t
+    S, F, IP = C.POINTER(SceneView), C.POINTER(Frame), C.POINTER(C.c_int32)
+    return {
+        'ptmi_version': (C.c_int, []),
+        'ptmi_last_error': (C.c_char_p, []),
+        'ptmi_scene_check': (C.c_int, [S]),
+        'ptmi_mk_render': (C.c_int, [S, F, P, I, I, P, P]),
+        'ptmi_mk_workspace_bytes': (Z, [F, I]),
+        'ptmi_mk_render_ws': (C.c_int, [S, F, P, Z, P, I, I, P, P]),
+        'ptmi_mk_trace_ws': (C.c_int, [S, F, P, Z, I, I, P, P]),
+        'ptmi_mk_max_batch': (C.c_int64, [F]),
+        'ptmi_mk_resolve_ws': (C.c_int, [F, P, Z, P, I, P]),
+        'ptmi_wf_workspace_bytes': (Z, [F, I]),
+        'ptmi_wf_render': (C.c_int, [S, F, P, Z, P, I, I, P, P]),
+        'ptmi_clear': (C.c_int, [F, P, P]),
+        'ptmi_tonemap': (C.c_int, [P, P, I, I, I, P]),
+        'ptmi_bvh_build_sah': (C.c_int, [P, I, P, I, P, I, P, P, P, P, P, P, P, IP]),
+        'ptmi_prof_start': (C.c_int, [I]),
+        'ptmi_prof_stop': (C.c_int, [P, P, I]),
+        'ptmi_prof_stop_busy': (C.c_int, [P, P, P, I]),
+        'ptmi_node_bytes': (C.c_int, []),
+        'ptmi_wf_set_drain_at': (C.c_int, [I]),
+        # ABI v8: per-pixel error estimates and adaptive tile sampling
+        'ptmi_mk_tile_grid': (C.c_int, [F, IP, IP, IP, IP]),
+        'ptmi_stats_clear': (C.c_int, [F, P, P]),
+        'ptmi_mk_trace_tiles_ws': (C.c_int, [S, F, P, Z, P, I, I, I, P, P]),
+        'ptmi_mk_resolve_stats_ws': (C.c_int, [F, P, Z, P, P, P, I, I, P]),
+        'ptmi_wf_render_stats': (C.c_int, [S, F, P, Z, P, P, I, I, P, P]),
+        'ptmi_tile_update': (C.c_int, [F, P, C.c_float, I, I, P, P, P, P, P]),
+        'ptmi_tonemap_stats': (C.c_int, [P, P, P, I, I, P]),
+    }
+
+
+SIGNATURES = _signatures()
+EXPORTS = tuple(SIGNATURES)
 PROF_KINDS = ('megakernel', 'wf_generate', 'wf_intersect', 'wf_drain', 'wf_scatter', 'wf_resolve', 'mk_resolve')
 
 _lib = None
@@ -90,43 +120,9 @@ def load(path: str = LIB_PATH):
     except ImportError:
         pass
     lib = C.CDLL(path)
-    P = C.c_void_p
-    lib.ptmi_version.restype = C.c_int
-    lib.ptmi_node_bytes.restype = C.c_int
-    lib.ptmi_last_error.restype = C.c_char_p
-    lib.ptmi_scene_check.argtypes = [C.POINTER(SceneView)]
-    lib.ptmi_mk_render.argtypes = [C.POINTER(SceneView), C.POINTER(Frame), P, C.c_int32, C.c_int32, P, P]
-    lib.ptmi_mk_workspace_bytes.argtypes = [C.POINTER(Frame), C.c_int32]
-    lib.ptmi_mk_workspace_bytes.restype = C.c_size_t
-    lib.ptmi_mk_max_batch.argtypes = [C.POINTER(Frame)]
-    lib.ptmi_mk_max_batch.restype = C.c_int64
-    lib.ptmi_mk_render_ws.argtypes = [C.POINTER(SceneView), C.POINTER(Frame), P, C.c_size_t, P, C.c_int32,
-                                      C.c_int32, P, P]
-    lib.ptmi_mk_trace_ws.argtypes = [C.POINTER(SceneView), C.POINTER(Frame), P, C.c_size_t, C.c_int32, C.c_int32,
-                                     P, P]
-    lib.ptmi_mk_resolve_ws.argtypes = [C.POINTER(Frame), P, C.c_size_t, P, C.c_int32, P]
-    lib.ptmi_wf_workspace_bytes.argtypes = [C.POINTER(Frame), C.c_int32]
-    lib.ptmi_wf_workspace_bytes.restype = C.c_size_t
-    lib.ptmi_wf_render.argtypes = [C.POINTER(SceneView), C.POINTER(Frame), P, C.c_size_t, P, C.c_int32,
-                                   C.c_int32, P, P]
-    lib.ptmi_wf_set_drain_at.argtypes = [C.c_int32]
-    lib.ptmi_clear.argtypes = [C.POINTER(Frame), P, P]
-    lib.ptmi_tonemap.argtypes = [P, P, C.c_int32, C.c_int32, C.c_int32, P]
-    lib.ptmi_bvh_build_sah.argtypes = [P, C.c_int32, P, C.c_int32, P, C.c_int32, P, P, P, P, P, P, P,
-                                       C.POINTER(C.c_int32)]
-    I32P = C.POINTER(C.c_int32)
-    lib.ptmi_mk_tile_grid.argtypes = [C.POINTER(Frame), I32P, I32P, I32P, I32P]
-    lib.ptmi_stats_clear.argtypes = [C.POINTER(Frame), P, P]
-    lib.ptmi_mk_trace_tiles_ws.argtypes = [C.POINTER(SceneView), C.POINTER(Frame), P, C.c_size_t, P, C.c_int32,
-                                           C.c_int32, C.c_int32, P, P]
-    lib.ptmi_mk_resolve_stats_ws.argtypes = [C.POINTER(Frame), P, C.c_size_t, P, P, P, C.c_int32, C.c_int32, P]
-    lib.ptmi_wf_render_stats.argtypes = [C.POINTER(SceneView), C.POINTER(Frame), P, C.c_size_t, P, P, C.c_int32,
-                                         C.c_int32, P, P]
-    lib.ptmi_tile_update.argtypes = [C.POINTER(Frame), P, C.c_float, C.c_int32, C.c_int32, P, P, P, P, P]
-    lib.ptmi_tonemap_stats.argtypes = [P, P, P, C.c_int32, C.c_int32, P]
-    lib.ptmi_prof_start.argtypes = [C.c_int32]
-    lib.ptmi_prof_stop.argtypes = [P, P, C.c_int32]
-    lib.ptmi_prof_stop_busy.argtypes = [P, P, P, C.c_int32]
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     if lib.ptmi_version() != ABI_VERSION:
         raise PtmiError(f'libptmi ABI version {lib.ptmi_version()} != {ABI_VERSION} (rebuild libptmi.so)')
     _lib = lib

@@ -94,7 +94,7 @@ class DeviceScene:
         v.num_bvh_nodes = layout.num_bvh_nodes if layout.ref_nodes is not None else \
             (2 * (layout.n_inner + 1) - 1 if layout.num_spheres + layout.num_quads + layout.num_triangles else 0)
         self.view = v
-        _lib.check(_lib.load().ptmi_scene_check(C.byref(v)), 'ptmi_scene_check')
+        _lib.check(_lib.load().ptmi_scene_check(v), 'ptmi_scene_check')
 
     @classmethod
     def from_arrays(cls, sa: SceneArrays, device=None):
@@ -148,9 +148,28 @@ class Integrator:
         self._ws = None
         self._ws_bytes = 0
         self._reset_event = None  # counter reset the next overlapped trace must wait for
+        self._ov = None  # side streams, workspaces and events of render_mk_overlapped, made by its first call
+        self._n_active = torch.zeros(1, dtype=torch.int32, device=dscene.device)  # tile_update's readback slot
+
+    def _call(self, name, *args):
+        """One C-ABI call by export name; a non-zero return raises PtmiError with ptmi_last_error()."""
+        return _lib.check(getattr(self.lib, name)(*args), name)
+
+    def _batch(self, frame, npix, sample_count, one_trace=False):
+        """Samples per batch of a call on the frame's npix pixels: all of them,
+        within the staging budget (12 B per sample and pixel) and, where a
+        batch is one trace (one_trace), within its 32-bit item ids
+        (ptmi_mk_max_batch)."""
+        n = min(int(sample_count), self.STAGING_BYTES // max(1, 12 * npix))
+        if one_trace:
+            max_batch = int(self.lib.ptmi_mk_max_batch(frame))
+            if max_batch < 1:
+                _lib.check(-1, 'ptmi_mk_max_batch')
+            n = min(n, max_batch)
+        return max(1, n)
 
     def _cnt(self):
-        return C.c_void_p(self.counters.data_ptr()) if self.counters is not None else None
+        return self.counters.data_ptr() if self.counters is not None else None
 
     def _dev(self):
         """Context that makes the scene's device current for a C-ABI call."""
@@ -175,16 +194,11 @@ class Integrator:
         with self._dev():
             if staged:
                 ws = self.workspace(frame, sample_count, 'mk')
-                _lib.check(self.lib.ptmi_mk_render_ws(C.byref(self.scene.view), C.byref(frame),
-                                                      C.c_void_p(ws.data_ptr()), self._ws_bytes,
-                                                      C.c_void_p(accum.data_ptr()), int(sample_begin),
-                                                      int(sample_count), self._cnt(), self._stream(stream)),
-                           'ptmi_mk_render_ws')
+                self._call('ptmi_mk_render_ws', self.scene.view, frame, ws.data_ptr(), self._ws_bytes,
+                           accum.data_ptr(), int(sample_begin), int(sample_count), self._cnt(), self._stream(stream))
                 return
-            _lib.check(self.lib.ptmi_mk_render(C.byref(self.scene.view), C.byref(frame),
-                                               C.c_void_p(accum.data_ptr()), int(sample_begin), int(sample_count),
-                                               self._cnt(), self._stream(stream)),
-                       'ptmi_mk_render')
+            self._call('ptmi_mk_render', self.scene.view, frame, accum.data_ptr(), int(sample_begin),
+                       int(sample_count), self._cnt(), self._stream(stream))
 
     # Staging budget for the per-(sample, pixel) colour slots of one batch:
     # 2 GiB keeps a whole 16-spp 4K call (1.6 GB) in one batch. A/B on MI355X
@@ -234,12 +248,9 @@ class Integrator:
         npix = frame.w * len(frame_pixel_rows(frame))
         if npix == 0 or sample_count <= 0:
             return
-        max_batch = int(self.lib.ptmi_mk_max_batch(C.byref(frame)))
-        if max_batch < 1:
-            _lib.check(-1, 'ptmi_mk_max_batch')
-        per = max(1, min(int(sample_count), self.STAGING_BYTES // max(1, 12 * npix), max_batch))
+        per = self._batch(frame, npix, sample_count, one_trace=True)
         with self._dev():
-            if getattr(self, '_ov', None) is None:
+            if self._ov is None:
                 D = self.OVERLAP_DEPTH_MAX
                 self._ov = {'streams': [torch.cuda.Stream(dev) for _ in range(D)], 'ws': [None] * D,
                             'k': 0, 'resolved': [None] * D, 'last_resolved': None, 'traced': [None] * D}
@@ -254,7 +265,7 @@ class Integrator:
                 n = min(per, int(sample_count) - b)
                 h = ov['k'] % depth  # any rotation is safe: each half waits for its own last reader
                 ov['k'] += 1
-                need = int(self.lib.ptmi_mk_workspace_bytes(C.byref(frame), n))
+                need = int(self.lib.ptmi_mk_workspace_bytes(frame, n))
                 if need == 0:
                     _lib.check(-1, 'ptmi_mk_workspace_bytes')
                 side = ov['streams'][h]
@@ -268,19 +279,16 @@ class Integrator:
                     side.wait_event(fresh)
                 if ov['resolved'][h] is not None:
                     side.wait_event(ov['resolved'][h])
-                _lib.check(self.lib.ptmi_mk_trace_ws(C.byref(self.scene.view), C.byref(frame),
-                                                     C.c_void_p(ws.data_ptr()), ws.numel() * 4,
-                                                     int(sample_begin) + b, n, self._cnt(),
-                                                     C.c_void_p(side.cuda_stream)), 'ptmi_mk_trace_ws')
+                self._call('ptmi_mk_trace_ws', self.scene.view, frame, ws.data_ptr(), ws.numel() * 4,
+                           int(sample_begin) + b, n, self._cnt(), side.cuda_stream)
                 traced = torch.cuda.Event()
                 traced.record(side)
                 ov['traced'][h] = traced
                 caller.wait_event(traced)
                 if ov['last_resolved'] is not None:
                     caller.wait_event(ov['last_resolved'])
-                _lib.check(self.lib.ptmi_mk_resolve_ws(C.byref(frame), C.c_void_p(ws.data_ptr()), ws.numel() * 4,
-                                                       C.c_void_p(accum.data_ptr()), n,
-                                                       C.c_void_p(caller.cuda_stream)), 'ptmi_mk_resolve_ws')
+                self._call('ptmi_mk_resolve_ws', frame, ws.data_ptr(), ws.numel() * 4, accum.data_ptr(), n,
+                           caller.cuda_stream)
                 done = torch.cuda.Event()
                 done.record(caller)
                 ov['resolved'][h] = done
@@ -290,10 +298,9 @@ class Integrator:
     def workspace(self, frame, sample_count=1, kind='wf'):
         """Cached device workspace (torch) big enough for one batch of the call
         (shared by the megakernel's staged mode and the wavefront)."""
-        npix = frame.w * len(frame_pixel_rows(frame))
-        batch = max(1, min(int(sample_count), self.STAGING_BYTES // max(1, 12 * npix)))
         fn = self.lib.ptmi_wf_workspace_bytes if kind == 'wf' else self.lib.ptmi_mk_workspace_bytes
-        need = int(fn(C.byref(frame), batch))
+        npix = frame.w * len(frame_pixel_rows(frame))
+        need = int(fn(frame, self._batch(frame, npix, sample_count)))
         if need == 0:
             _lib.check(-1, f'ptmi_{kind}_workspace_bytes')
         if self._ws is None or self._ws_bytes < need:
@@ -306,16 +313,13 @@ class Integrator:
         _check_accum(accum, frame, self.scene.device)
         with self._dev():
             ws = self.workspace(frame, sample_count)
-            _lib.check(self.lib.ptmi_wf_render(C.byref(self.scene.view), C.byref(frame), C.c_void_p(ws.data_ptr()),
-                                               self._ws_bytes, C.c_void_p(accum.data_ptr()), int(sample_begin),
-                                               int(sample_count), self._cnt(), self._stream(stream)),
-                       'ptmi_wf_render')
+            self._call('ptmi_wf_render', self.scene.view, frame, ws.data_ptr(), self._ws_bytes, accum.data_ptr(),
+                       int(sample_begin), int(sample_count), self._cnt(), self._stream(stream))
 
     def clear(self, frame, accum, stream=None):
         _check_accum(accum, frame, self.scene.device)
         with self._dev():
-            _lib.check(self.lib.ptmi_clear(C.byref(frame), C.c_void_p(accum.data_ptr()), self._stream(stream)),
-                       'ptmi_clear')
+            self._call('ptmi_clear', frame, accum.data_ptr(), self._stream(stream))
 
     def tonemap(self, accum, spp=None, stats=None, stream=None):
         """u8 image of accum divided by ``spp``, or, with ``stats``, by each
@@ -329,19 +333,17 @@ class Integrator:
             out = torch.empty((h, w, 3), dtype=torch.uint8, device=accum.device)
             if stats is not None:
                 _check_stats(stats, h, w, self.scene.device)
-                _lib.check(self.lib.ptmi_tonemap_stats(C.c_void_p(accum.data_ptr()), C.c_void_p(stats.data_ptr()),
-                                                       C.c_void_p(out.data_ptr()), w, h, self._stream(stream)),
-                           'ptmi_tonemap_stats')
+                self._call('ptmi_tonemap_stats', accum.data_ptr(), stats.data_ptr(), out.data_ptr(), w, h,
+                           self._stream(stream))
                 return out
-            _lib.check(self.lib.ptmi_tonemap(C.c_void_p(accum.data_ptr()), C.c_void_p(out.data_ptr()), w, h,
-                                             int(spp), self._stream(stream)), 'ptmi_tonemap')
+            self._call('ptmi_tonemap', accum.data_ptr(), out.data_ptr(), w, h, int(spp), self._stream(stream))
         return out
 
     # ------------------------------------------ error estimates, adaptive tiles
     def tile_grid(self, frame):
         """(tile_w, tile_h, tiles_x, tiles_y) of the frame's 64-pixel megakernel tiles."""
         v = [C.c_int32() for _ in range(4)]
-        _lib.check(self.lib.ptmi_mk_tile_grid(C.byref(frame), *[C.byref(x) for x in v]), 'ptmi_mk_tile_grid')
+        self._call('ptmi_mk_tile_grid', frame, *v)
         return tuple(int(x.value) for x in v)
 
     def new_stats(self, frame):
@@ -359,8 +361,7 @@ class Integrator:
     def clear_stats(self, frame, stats, stream=None):
         _check_stats(stats, frame.height, frame.width, self.scene.device)
         with self._dev():
-            _lib.check(self.lib.ptmi_stats_clear(C.byref(frame), C.c_void_p(stats.data_ptr()), self._stream(stream)),
-                       'ptmi_stats_clear')
+            self._call('ptmi_stats_clear', frame, stats.data_ptr(), self._stream(stream))
 
     def render_mk_stats(self, frame, accum, stats, sample_begin, sample_count, tiles=None, stream=None):
         """Megakernel samples [sample_begin, sample_begin + sample_count) added
@@ -380,29 +381,21 @@ class Integrator:
         npix = frame.w * len(frame_pixel_rows(frame))
         if npix == 0 or sample_count <= 0 or (tl is not None and nt == 0):
             return
-        max_batch = int(self.lib.ptmi_mk_max_batch(C.byref(frame)))
-        if max_batch < 1:
-            _lib.check(-1, 'ptmi_mk_max_batch')
-        per = max(1, min(sample_count, self.STAGING_BYTES // max(1, 12 * npix), max_batch))
+        per = self._batch(frame, npix, sample_count, one_trace=True)
         with self._dev():
             ws = self.workspace(frame, per, 'mk')
-            wp, sp = C.c_void_p(ws.data_ptr()), self._stream(stream)
+            wp, sp = ws.data_ptr(), self._stream(stream)
+            tp = tl.data_ptr() if tl is not None else None
             for b in range(0, sample_count, per):
                 n = min(per, sample_count - b)
                 if tl is None:
-                    _lib.check(self.lib.ptmi_mk_trace_ws(C.byref(self.scene.view), C.byref(frame), wp, self._ws_bytes,
-                                                         int(sample_begin) + b, n, self._cnt(), sp),
-                               'ptmi_mk_trace_ws')
+                    self._call('ptmi_mk_trace_ws', self.scene.view, frame, wp, self._ws_bytes, int(sample_begin) + b,
+                               n, self._cnt(), sp)
                 else:
-                    _lib.check(self.lib.ptmi_mk_trace_tiles_ws(C.byref(self.scene.view), C.byref(frame), wp,
-                                                               self._ws_bytes, C.c_void_p(tl.data_ptr()), nt,
-                                                               int(sample_begin) + b, n, self._cnt(), sp),
-                               'ptmi_mk_trace_tiles_ws')
-                _lib.check(self.lib.ptmi_mk_resolve_stats_ws(C.byref(frame), wp, self._ws_bytes,
-                                                             C.c_void_p(accum.data_ptr()),
-                                                             C.c_void_p(stats.data_ptr()),
-                                                             C.c_void_p(tl.data_ptr()) if tl is not None else None,
-                                                             nt, n, sp), 'ptmi_mk_resolve_stats_ws')
+                    self._call('ptmi_mk_trace_tiles_ws', self.scene.view, frame, wp, self._ws_bytes, tp, nt,
+                               int(sample_begin) + b, n, self._cnt(), sp)
+                self._call('ptmi_mk_resolve_stats_ws', frame, wp, self._ws_bytes, accum.data_ptr(), stats.data_ptr(),
+                           tp, nt, n, sp)
 
     def render_wf_stats(self, frame, accum, stats, sample_begin, sample_count, stream=None):
         """render_wf resolving through the stats resolve (whole frame only)."""
@@ -410,26 +403,19 @@ class Integrator:
         _check_stats(stats, frame.height, frame.width, self.scene.device)
         with self._dev():
             ws = self.workspace(frame, sample_count)
-            _lib.check(self.lib.ptmi_wf_render_stats(C.byref(self.scene.view), C.byref(frame),
-                                                     C.c_void_p(ws.data_ptr()), self._ws_bytes,
-                                                     C.c_void_p(accum.data_ptr()), C.c_void_p(stats.data_ptr()),
-                                                     int(sample_begin), int(sample_count), self._cnt(),
-                                                     self._stream(stream)), 'ptmi_wf_render_stats')
+            self._call('ptmi_wf_render_stats', self.scene.view, frame, ws.data_ptr(), self._ws_bytes,
+                       accum.data_ptr(), stats.data_ptr(), int(sample_begin), int(sample_count), self._cnt(),
+                       self._stream(stream))
 
     def tile_update(self, frame, stats, threshold, min_spp, max_spp, tiles, stream=None):
         """Tile errors and states from stats (ptmi_tile_update) into the
         buffers of ``tiles`` (new_tiles); returns the number of active tiles
         (one 4-byte readback) and stores it as tiles['n']."""
         _check_stats(stats, frame.height, frame.width, self.scene.device)
-        if getattr(self, '_n_active', None) is None:
-            self._n_active = torch.zeros(1, dtype=torch.int32, device=self.scene.device)
         with self._dev():
-            _lib.check(self.lib.ptmi_tile_update(C.byref(frame), C.c_void_p(stats.data_ptr()), float(threshold),
-                                                 int(min_spp), int(max_spp), C.c_void_p(tiles['state'].data_ptr()),
-                                                 C.c_void_p(tiles['err'].data_ptr()),
-                                                 C.c_void_p(tiles['list'].data_ptr()),
-                                                 C.c_void_p(self._n_active.data_ptr()), self._stream(stream)),
-                       'ptmi_tile_update')
+            self._call('ptmi_tile_update', frame, stats.data_ptr(), float(threshold), int(min_spp), int(max_spp),
+                       tiles['state'].data_ptr(), tiles['err'].data_ptr(), tiles['list'].data_ptr(),
+                       self._n_active.data_ptr(), self._stream(stream))
             if stream is not None:
                 stream.synchronize()
             tiles['n'] = int(self._n_active.item())
@@ -438,9 +424,8 @@ class Integrator:
     def _after_traces(self, stream):
         """Make `stream` wait for the overlapped traces in flight: they add to
         the counters from their side streams."""
-        ov = getattr(self, '_ov', None)
-        if ov is not None:
-            for ev in ov['traced']:
+        if self._ov is not None:
+            for ev in self._ov['traced']:
                 if ev is not None:
                     stream.wait_event(ev)
 
@@ -472,9 +457,8 @@ class Integrator:
             # side streams, so waiting on the first one only is not enough)
             ev = torch.cuda.Event()
             ev.record(s)
-            ov = getattr(self, '_ov', None)
-            if ov is not None:
-                for side in ov['streams']:
+            if self._ov is not None:
+                for side in self._ov['streams']:
                     side.wait_event(ev)
             self._reset_event = ev  # side streams created after this reset wait on it too
 

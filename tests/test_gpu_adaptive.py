@@ -229,6 +229,48 @@ def test_listed_trace(integs):
     assert cnt == {k: int(v) for k, v in ost.items()}
 
 
+def _rung(slots):
+    """The staged megakernel's traversal kernel for max_leaf_depth + 1 stack slots."""
+    return next((r for r in (16, 17, 18, 19, 20, 24, 32, 64) if slots <= r and slots <= 63), 'reference walk')
+
+
+@pytest.mark.parametrize('name,traversal,rung', [
+    ('chain17', 'stack', 17), ('chain18', 'stack', 18), ('chain19', 'stack', 19), ('chain20', 'stack', 20),
+    ('chain22', 'stack', 24), ('chain29', 'stack', 32), ('chain52', 'stack', 64),
+    ('chainx70', 'stack', 'reference walk'), ('chain22', 'stackless', 24)])
+def test_listed_trace_on_every_traversal_rung(name, traversal, rung):
+    """The listed trace of every rung of the traversal dispatch but the 16-slot
+    one (test_listed_trace) against the unlisted trace, which test_gpu_edge
+    ties to the oracle: bit-equal on the listed tiles, nothing else touched.
+    32 x 18: 4 x 3 tiles of 8 x 8, the last row of tiles 2 pixels high."""
+    import torch
+    from edge_scenes import edge_scene
+    from ptmi import device
+    sa, cam, bg = edge_scene(name, 32)
+    W, H, spp = cam['width'], cam['height'], 3
+    assert (W, H) == (32, 18)
+    integ = device.Integrator(device.DeviceScene.from_arrays(sa))
+    assert _rung(integ.scene.layout.max_leaf_depth + 1) == rung
+    fr = device.make_frame(cam, bg, 50, 3, W, H, traversal=traversal)
+    assert integ.tile_grid(fr) == (8, 8, 4, 3)
+    ids = np.array([1, 4, 6, 9, 11], np.int32)
+    dev_list = torch.from_numpy(np.array([1, -3, 4, 6, 12, 9, 1 << 30, 11], np.int32)).cuda()  # 3 ids outside the grid
+    listed = ah.tile_mask(W, H, 8, 8, ids)
+    assert listed.sum() == 64 * 3 + 16 * 2  # tiles 9 and 11 are 8 x 2
+    whole = pattern(fr, 3, 0.5), pattern(fr, 4, 1.25)
+    part = pattern(fr, 3, 0.5), pattern(fr, 4, 1.25)
+    pat = [host(t).copy() for t in part]
+    integ.render_mk_stats(fr, *whole, 0, spp)
+    integ.reset_counters()
+    integ.render_mk_stats(fr, *part, 0, spp, tiles=(dev_list, dev_list.numel()))
+    for got, ref, untouched in zip(part, whole, pat):
+        got, ref = host(got), host(ref)
+        assert eq(got[listed], ref[listed])
+        assert eq(got[~listed], untouched[~listed])
+        assert not eq(ref[~listed], untouched[~listed])  # the unlisted trace did render there
+    assert integ.read_counters()['paths'] == int(listed.sum()) * spp
+
+
 # ---------------------------------------------------------------- 6: adaptive end to end
 @pytest.mark.parametrize('always_listed', [False, True], ids=['plain-first-pass', 'listed-first-pass'])
 def test_adaptive_end_to_end(integs, always_listed):
