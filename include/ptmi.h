@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define PTMI_ABI_VERSION 8
+#define PTMI_ABI_VERSION 9
 #define PTMI_MAX_IMAGES 16
 
 enum {
@@ -72,6 +72,29 @@ enum {
  *             when the node is its parent's left child, else 1. Used by the
  *             stackless traversal and by BVHs of leaf depth > 62 (the
  *             reference's 64-entry stack walk); may be NULL otherwise.
+ *   shell   : enclosing medium shell hint (ABI v9). 0: none (a zeroed view
+ *             keeps every kernel on its ordinary path). Otherwise 1 + the
+ *             BYTE offset in nodes of the node that holds the shell's leaf as
+ *             a child + the child index (0 or 1); offsets are multiples of
+ *             ptmi_node_bytes(), so the low bit is free. Any other offset, or
+ *             one past n_inner nodes, is PTMI_EINVAL. The shell is a
+ *             constant-medium sphere S (centre c, radius R) around the whole
+ *             scene, e.g. the global fog of a "final scene". The caller claims,
+ *             as it does for the class bits of a leaf code:
+ *               1. S is a sphere leaf of class PTMI_CLASS_MEDIUM with finite
+ *                  R > 0, and its leaf is not the BVH root;
+ *               2. the farthest corner of every other leaf's box lies within
+ *                  R / 2 of c (evaluated in f64);
+ *               3. max_leaf_depth <= 62 (the ordinary stack walk is used).
+ *             The megakernel's stack-walk kernels of 16, 17, 18 and 20 slots
+ *             (leaf depth <= 17, or 19) then resolve, for a path segment that starts within R / 2 of c
+ *             (4 |o - c|^2 <= R^2 in f32) and ends on S, the medium's exit
+ *             search and, after a passthrough, the segment that leaves the
+ *             scene from the shell leaf's own box and sphere alone, without
+ *             the two BVH traversals: under 1-3 nothing else can be hit on
+ *             either, so results and counters are unchanged bit for bit.
+ *             Every other kernel (other stack sizes, the stackless and the
+ *             reference stack walk, the wavefront) ignores the hint.
  */
 typedef struct ptmi_scene_view {
     const float *nodes;
@@ -95,6 +118,7 @@ typedef struct ptmi_scene_view {
     const int32_t *perlin_perm;
     const float *ref_nodes;
     int32_t num_bvh_nodes;     /* all nodes: 2 x primitives - 1 (0 for an empty world) */
+    int32_t shell;             /* enclosing medium shell hint, 0 = none (see above; ABI v9) */
 } ptmi_scene_view;
 
 /* Camera upload values (renderer.py:230-247 / fields.py:159-165). */

@@ -130,6 +130,15 @@ static int to_dev_scene(const ptmi_scene_view* s, DevScene& d) {
   if (s->num_bvh_nodes != (np > 0 ? 2 * np - 1 : 0))
     return fail(PTMI_EINVAL, "num_bvh_nodes %d for %d primitives (expected 2N-1)", s->num_bvh_nodes, np);
   if (s->ref_nodes && !aligned16(s->ref_nodes)) return fail(PTMI_EINVAL, "ref_nodes misaligned");
+  // Shell hint (include/ptmi.h): 1 + node byte offset + child index. The
+  // kernels read that node, so the offset is checked; what it claims about the
+  // scene is the caller's, like a leaf code's class bits.
+  if (s->shell != 0) {
+    const int64_t off = ((int64_t)s->shell - 1) & ~(int64_t)1;
+    if (s->shell < 0 || off % kNodeBytes != 0 || off / kNodeBytes >= s->n_inner)
+      return fail(PTMI_EINVAL, "shell %d is not 1 + a node offset (multiple of %u, below %d nodes) + child index",
+                  s->shell, kNodeBytes, s->n_inner);
+  }
   std::memset(&d, 0, sizeof d);
   d.nodes = (const float4*)s->nodes;
   d.n_inner = s->n_inner;
@@ -156,6 +165,7 @@ static int to_dev_scene(const ptmi_scene_view* s, DevScene& d) {
   d.perlin_perm = s->perlin_perm;
   d.ref_nodes = (const float4*)s->ref_nodes;
   d.n_nodes = s->num_bvh_nodes;
+  d.shell = s->max_leaf_depth <= 62 ? s->shell : 0;
   return PTMI_OK;
 }
 

@@ -71,6 +71,7 @@ struct DevScene {
   const int32_t* __restrict__ perlin_perm;
   const float4* __restrict__ ref_nodes;  // reference-layout nodes (stackless traversal), 3 float4 each
   int32_t n_nodes;                       // all BVH nodes
+  int32_t shell;                         // enclosing medium shell hint (include/ptmi.h), 0 = none; in the struct's tail padding
 };
 
 struct DevFrame {
@@ -954,6 +955,64 @@ __device__ __forceinline__ bool traverse(const DevScene& sc, pt_v3 o, pt_v3 d, f
   t_out = tr.closest;
   ref_out = tr.best;
   return tr.any();
+}
+
+// ---------------------------------------------------------------- enclosing medium shell
+// The scene's shell hint (DevScene::shell, include/ptmi.h): a constant-medium
+// sphere around everything else. A traversal (Trav, closest = kTMax) of a ray
+// that can hit nothing but the shell reaches the shell's leaf exactly when the
+// leaf's own box passes the slab test: every ancestor's box contains it and
+// (b - o) * inv is monotone in b under f32 rounding, so the ancestors pass
+// too, and with no other hit no pop is culled. shell_hit is that traversal's
+// result from the leaf's box and sphere alone, with the traversal's own
+// functions (slab, hit_sphere_t<true>) on its own inv, so the bits match.
+struct Shell {
+  float4 sph;                      // {c.xyz, R}
+  float lox, loy, loz, hix, hiy, hiz;  // the leaf's box, as its parent node stores it
+  int32_t ref;                     // the leaf's code
+};
+
+typedef const __attribute__((address_space(4))) float pt_cf;
+typedef float pt_f4v __attribute__((ext_vector_type(4)));  // clang vector type: no C++ copy constructor
+typedef const __attribute__((address_space(4))) pt_f4v pt_cf4;
+
+// Wave-uniform: the node at the hint's byte offset (checked on the host), child
+// 0 or 1 of it. The sphere is left to the caller, which loads it
+// (load_shell_sphere) only for a lane whose traversal hit this very leaf as a
+// sphere, a load the traversal itself made, so a wrong hint reads nothing out
+// of bounds.
+__device__ __forceinline__ Shell load_shell_box(const DevScene& sc) {
+  const uint32_t v = (uint32_t)sc.shell - 1u, c = v & 1u;
+  // constant address space: the scene is read-only while a kernel runs, and a
+  // uniform address there is fetched by the scalar unit into SGPRs, not by 64
+  // lanes through the texture-address unit, the megakernel's busiest (DESIGN.md
+  // §5). A/B on MI355X against plain pointers, same bits: C2 +0.3 %, C5 +0.5 %,
+  // every run above every run (profiles/shell/bench_parent_vs_new.json)
+  const pt_cf* nd = (const pt_cf*)((uintptr_t)sc.nodes + (v & ~1u));
+  Shell sh;
+  sh.lox = nd[0 + c];
+  sh.loy = nd[2 + c];
+  sh.loz = nd[4 + c];
+  sh.hix = nd[6 + c];
+  sh.hiy = nd[8 + c];
+  sh.hiz = nd[10 + c];
+  sh.ref = __float_as_int(nd[12 + c]);
+  sh.sph = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  return sh;
+}
+
+// The shell's sphere, for a lane whose hit is the shell's leaf (uniform address).
+__device__ __forceinline__ float4 load_shell_sphere(const DevScene& sc, const Shell& sh) {
+  const pt_f4v s = *(const pt_cf4*)((uintptr_t)sc.spheres + 16u * (uint32_t)leaf_index(sh.ref));
+  return make_float4(s.x, s.y, s.z, s.w);
+}
+
+// Closest hit in [tmin, kTMax) of a ray that can hit nothing but the shell.
+__device__ __forceinline__ bool shell_hit(const Shell& sh, pt_v3 o, pt_v3 d, pt_v3 inv, float tmin, float& t) {
+  float E, X;
+  slab(o, inv, sh.lox, sh.loy, sh.loz, sh.hix, sh.hiy, sh.hiz, tmin, E, X);
+  if (!(pt_minf(X, kTMax) >= E)) return false;
+  return hit_sphere_t<true>(sh.sph, o, d, tmin, kTMax, t);
 }
 
 // ---------------------------------------------------------------- textures

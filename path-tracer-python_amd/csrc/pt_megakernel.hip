@@ -22,6 +22,9 @@
 //     only the tiles of a device list, mapped in locate(); the unlisted
 //     instantiations compile to the code they were without the flag
 //     (profiles/adaptive/resources.md);
+//   * enclosing medium shell (SHELL): in a scene wrapped in a fog sphere a
+//     path that leaves through it decides its exit search and its last
+//     segment in the shading round of the shell hit, without traversing;
 //   * BVH: child-box BVH2 nodes (80 B, one node load tests both children),
 //     traversal stack in LDS (slot-major, conflict-free), see pt_device.hpp.
 // Perlin corner loop fully unrolled here (A/B on MI355X: +2.5 % megakernel,
@@ -250,12 +253,23 @@ static int64_t mk_tiles(const DevFrame& fr, int32_t* tx_out = nullptr) {
   return tx * ty;
 }
 
-template <int STACK, bool STAGED, int TRAV = PTMI_TRAV_STACK, bool LISTED = false>
+template <int STACK, bool STAGED, int TRAV = PTMI_TRAV_STACK, bool LISTED = false, bool SHELL = false>
 // waves/SIMD the LDS stack allows: 160 KiB / (STACK * 8 B * 256) blocks per CU
 // (16 -> 5, 20 -> 4, 24 -> 3, 32 -> 2), and the VGPR budget of that many
 // waves (96 at 5, 128 at 4).
 // TRAV = PTMI_TRAV_STACKLESS (STACK 1: no stack) walks the reference's
 // stackless traversal instead (TravSL, pt_device.hpp).
+// SHELL (the scene has an enclosing medium shell, DevScene::shell): a lane
+// whose segment began within R / 2 of the shell's centre and ended on the
+// shell resolves the medium's exit search, and after a passthrough the
+// segment that leaves the scene, in the same shading round from the shell's
+// own leaf box and sphere (shell_hit, pt_device.hpp) instead of two more
+// traversals and two more shading rounds. vol2: 41 % of all traversals, 84 %
+// of the paths end this way. A template flag, chosen by the
+// dispatch for stack-walk kernels of 16 to 20 slots (kMkShellRung): without
+// it the kernels are the code they were (profiles/shell/resources.md). A/B on
+// MI355X against the parent commit, bit-identical: C2 +19 %, C5 +24 %, C3 and
+// C4 unchanged (profiles/shell/bench_parent_vs_new.json).
 __global__ __launch_bounds__(kMkBlock, stress_waves(STACK < 20 ? PTMI_MK_MIN_WAVES_16 : STACK <= 20 ? PTMI_MK_MIN_WAVES : 1)) void mk_render_kernel(
     DevScene sc, DevFrame fr, float* __restrict__ accum, int32_t s_begin, int32_t s_count, int32_t chunk,
     float* __restrict__ staging, unsigned long long* __restrict__ counters, MkWork wk) {
@@ -453,17 +467,20 @@ __global__ __launch_bounds__(kMkBlock, stress_waves(STACK < 20 ? PTMI_MK_MIN_WAV
     // (medium scatter, metal fuzz, isotropic), which runs in wave-uniform code
     // so that the wave can share its rejection loop (random_unit_vector_wave).
     bool done = false, scattered = false, passthrough = false, to_medium = false;
+    bool esc_miss = false;  // SHELL: a passthrough whose next segment, from outside the shell, misses
     pt_v3 hp = pt_v3f(0.0f, 0.0f, 0.0f), sdir = hp, att = hp, n = hp;
     int32_t ruv = kRuvNone, sref = 0;
     float4 m0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // the metal's albedo and fuzz (scatter_end)
     PT_P4(1)  // wave turbulence
     if (shade_now) {  // segment traced: shade it
       trav = false;
-      const bool exit_mode = ps.mode == kModeMediumExit;
-      const bool hit = tr.any();
-      const float t = tr.closest;
+      bool exit_mode = ps.mode == kModeMediumExit;
+      bool hit = tr.any();
+      float t = tr.closest;
       const int32_t ref = tr.best;
       int32_t g = -1;
+      Shell sh{};          // SHELL: the shell's leaf box and sphere
+      bool inl = false;    // SHELL: this lane resolves its exit search (and escape segment) here
       if (!exit_mode) {
         if (!hit) {
           ps.color = pt_add(ps.color, pt_mul(ps.thr, bg));  // kernels.py:1164-1168
@@ -471,10 +488,26 @@ __global__ __launch_bounds__(kMkBlock, stress_waves(STACK < 20 ? PTMI_MK_MIN_WAV
         } else {
           g = mat_index(sc, ref);
           if (leaf_class(ref) == PTMI_CLASS_MEDIUM) {  // medium boundary (class in the leaf code): exit search next
-            ps.mode = kModeMediumExit;
             ps.t_entry = t;
             ps.ref_entry = ref;
-            to_medium = true;
+            if constexpr (SHELL) {
+              sh = load_shell_box(sc);
+              if (ref == sh.ref && leaf_type(ref) == kSphere) {
+                sh.sph = load_shell_sphere(sc, sh);
+                const pt_v3 oc = pt_sub(ps.o, pt_v3f(sh.sph.x, sh.sph.y, sh.sph.z));
+                inl = 4.0f * pt_dot(oc, oc) <= sh.sph.w * sh.sph.w;  // the gate: the segment began within R / 2 of the centre
+              }
+            }
+            if (inl) {  // the exit search (kernels.py:417) as this lane's own traversal would find it
+              ++n_med;
+              float te = kTMax;
+              hit = shell_hit(sh, ps.o, ps.dir, tr.inv, t + 0.0001f, te);
+              t = te;
+              exit_mode = true;
+            } else {
+              ps.mode = kModeMediumExit;
+              to_medium = true;
+            }
           }
         }
       } else {
@@ -500,6 +533,10 @@ __global__ __launch_bounds__(kMkBlock, stress_waves(STACK < 20 ? PTMI_MK_MIN_WAV
             float rl = sqrtf(pt_dot(ps.dir, ps.dir));
             float eps_t = 0.001f / rl;
             ps.o = pt_add(ps.o, pt_scale(ps.dir, t_exit + eps_t));
+            if constexpr (SHELL) {  // the segment from outside the shell: it misses unless the shell is hit again
+              float te;
+              if (inl) esc_miss = !shell_hit(sh, ps.o, ps.dir, tr.inv, kTMin, te);
+            }
           } else {  // fallback: shade the boundary as a surface, kernels.py:1111-1119
             surface = true;
             sref = ps.ref_entry;
@@ -555,6 +592,10 @@ __global__ __launch_bounds__(kMkBlock, stress_waves(STACK < 20 ? PTMI_MK_MIN_WAV
           if (ps.depth >= fr.max_depth) {
             done = true;
             ++n_cap;
+          } else if (SHELL && esc_miss) {  // that segment, traced and missed (kernels.py:1164-1168)
+            ++n_seg;
+            ps.color = pt_add(ps.color, pt_mul(ps.thr, bg));
+            done = true;
           }
         } else {
           done = true;
@@ -744,23 +785,37 @@ hipError_t launch_stage_resolve(const DevFrame& fr, const float* staging, int32_
   return hipGetLastError();
 }
 
-template <int STACK, int TRAV = PTMI_TRAV_STACK>
+template <int STACK, int TRAV = PTMI_TRAV_STACK, bool SHELL = false>
 static hipError_t launch_mk(const DevScene& sc, const DevFrame& fr, float* accum, int32_t s_begin,
                             int32_t s_count, unsigned long long* counters, hipStream_t stream) {
   dim3 grid((unsigned)((fr.w + kMkTile - 1) / kMkTile), (unsigned)((fr.n_rows + kMkTile - 1) / kMkTile));
   const int pslot = prof_begin(kProfMk, stream);
-  hipLaunchKernelGGL((mk_render_kernel<STACK, false, TRAV>), grid, dim3(kMkBlock), 0, stream, sc, fr, accum, s_begin,
+  hipLaunchKernelGGL((mk_render_kernel<STACK, false, TRAV, false, SHELL>), grid, dim3(kMkBlock), 0, stream, sc, fr, accum, s_begin,
                      s_count, s_count, (float*)nullptr, counters, MkWork{});
   prof_end(pslot, stream);
   return hipGetLastError();
 }
 
+// The SHELL kernels exist for the stack walk at 16 to 20 slots (vol2's 16, the
+// fine rungs up to C4-sized BVHs); every other rung ignores the scene's hint.
+// Not at 19 slots: with the flag that kernel takes 135 VGPRs, past the
+// 128 of its 4 waves/SIMD (profiles/shell/resources.md), and no scene here
+// runs it to say whether that pays.
+template <int STACK, int TRAV>
+constexpr bool kMkShellRung = TRAV == PTMI_TRAV_STACK && STACK >= 16 && STACK <= 20 && STACK != 19;
+
 hipError_t mk_render(const DevScene& sc, const DevFrame& fr, int32_t stack_needed, float* accum,
                      int32_t s_begin, int32_t s_count, unsigned long long* counters, hipStream_t stream) {
-  return dispatch_traversal<false>(fr, stack_needed, [&](auto stack, auto trav) {
-    constexpr int S = decltype(stack)::value, T = decltype(trav)::value;
-    return launch_mk<S, T>(sc, fr, accum, s_begin, s_count, counters, stream);
-  });
+  // SHELL wraps the ladder, plain kernels first (see mk_trace_staged)
+  auto render = [&](auto shell) {
+    return dispatch_traversal<false>(fr, stack_needed, [&](auto stack, auto trav) {
+      constexpr int S = decltype(stack)::value, T = decltype(trav)::value;
+      return launch_mk<S, T, decltype(shell)::value && kMkShellRung<S, T>>(sc, fr, accum, s_begin, s_count, counters,
+                                                                         stream);
+    });
+  };
+  if (sc.shell == 0) return render(std::false_type{});
+  return render(std::true_type{});
 }
 
 // ---------------------------------------------------------------- staged
@@ -778,7 +833,7 @@ size_t mk_workspace_bytes(int32_t npix, int32_t batch) {  // staging + the shard
 // resolve is launch_stage_resolve, on the caller's schedule).
 // LISTED: only the tiles of tile_list[0 .. n_list) are traced (units are sized
 // from the list length; staging keeps its [sample][frame pixel] layout).
-template <int STACK, int TRAV = PTMI_TRAV_STACK, bool LISTED = false>
+template <int STACK, int TRAV = PTMI_TRAV_STACK, bool LISTED = false, bool SHELL = false>
 static hipError_t launch_mk_trace(const DevScene& sc, const DevFrame& fr, float* staging, int32_t s_begin,
                                   int32_t nb, unsigned long long* counters, hipStream_t stream,
                                   const int32_t* tile_list, int32_t n_list) {
@@ -791,7 +846,7 @@ static hipError_t launch_mk_trace(const DevScene& sc, const DevFrame& fr, float*
   hipError_t e0 = hipGetDevice(&dev);
   if (e0 == hipSuccess) e0 = hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
   if (e0 == hipSuccess)
-    e0 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, mk_render_kernel<STACK, true, TRAV, LISTED>, kMkBlock, 0);
+    e0 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, mk_render_kernel<STACK, true, TRAV, LISTED, SHELL>, kMkBlock, 0);
   if (e0 != hipSuccess) return e0;
   MkWork wk;
   wk.ctl = (int32_t*)((char*)staging + mk_staging_bytes(fr.w * fr.n_rows, nb));
@@ -828,7 +883,7 @@ static hipError_t launch_mk_trace(const DevScene& sc, const DevFrame& fr, float*
   e0 = hipMemsetAsync(wk.ctl, 0, 256 * kMkShards, stream);
   if (e0 != hipSuccess) return e0;  // never launch on stale work counters
   const int pslot = prof_begin(kProfMk, stream);
-  hipLaunchKernelGGL((mk_render_kernel<STACK, true, TRAV, LISTED>), dim3((unsigned)waves), dim3(kMkBlock), 0, stream,
+  hipLaunchKernelGGL((mk_render_kernel<STACK, true, TRAV, LISTED, SHELL>), dim3((unsigned)waves), dim3(kMkBlock), 0, stream,
                      sc, fr, accum, s_begin, nb, nb, staging, counters, wk);
   prof_end(pslot, stream);
   return hipGetLastError();
@@ -842,14 +897,20 @@ hipError_t mk_trace_staged(const DevScene& sc, const DevFrame& fr, int32_t stack
   // LISTED wraps the ladder rather than branching inside its callable, unlisted
   // first: the code object then holds the unlisted kernels before the listed
   // ones, rung by rung, as it always has.
-  auto trace = [&](auto listed) {
+  // SHELL wraps both in the same way: the kernels without the flag come first.
+  auto trace = [&](auto listed, auto shell) {
     return dispatch_traversal<true>(fr, stack_needed, [&](auto stack, auto trav) {
-      return launch_mk_trace<decltype(stack)::value, decltype(trav)::value, decltype(listed)::value>(
+      constexpr int S = decltype(stack)::value, T = decltype(trav)::value;
+      return launch_mk_trace<S, T, decltype(listed)::value, decltype(shell)::value && kMkShellRung<S, T>>(
           sc, fr, (float*)ws, s_begin, nb, counters, stream, tile_list, n);
     });
   };
-  if (!tile_list) return trace(std::false_type{});
-  return trace(std::true_type{});
+  if (sc.shell == 0) {
+    if (!tile_list) return trace(std::false_type{}, std::false_type{});
+    return trace(std::true_type{}, std::false_type{});
+  }
+  if (!tile_list) return trace(std::false_type{}, std::true_type{});
+  return trace(std::true_type{}, std::true_type{});
 }
 
 void mk_tile_grid(const DevFrame& fr, int32_t* tile_w, int32_t* tile_h, int32_t* tiles_x, int32_t* tiles_y) {

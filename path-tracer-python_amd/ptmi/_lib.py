@@ -11,7 +11,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('PTMI_LIB') or os.path.join(_HERE, '_lib', 'libptmi.so')  # PTMI_LIB: A/B builds
-ABI_VERSION = 8  # PTMI_ABI_VERSION of include/ptmi.h
+ABI_VERSION = 9  # PTMI_ABI_VERSION of include/ptmi.h
 MAX_IMAGES = 16
 NUM_COUNTERS = 6
 COUNTER_TAIL_SEGMENTS = 5  # wavefront segments traced in the tail launch (wf_drain), part of [0]
@@ -32,6 +32,7 @@ class SceneView(C.Structure):
         ('img_h', C.c_int32 * MAX_IMAGES),
         ('perlin_vec', C.c_void_p), ('perlin_perm', C.c_void_p),
         ('ref_nodes', C.c_void_p), ('num_bvh_nodes', C.c_int32),
+        ('shell', C.c_int32),  # enclosing medium shell hint (scene_data.find_shell), 0 = none
     ]
 
 

@@ -93,6 +93,7 @@ class DeviceScene:
             v.ref_nodes = self.t_ref_nodes.data_ptr()
         v.num_bvh_nodes = layout.num_bvh_nodes if layout.ref_nodes is not None else \
             (2 * (layout.n_inner + 1) - 1 if layout.num_spheres + layout.num_quads + layout.num_triangles else 0)
+        v.shell = int(layout.shell)
         self.view = v
         _lib.check(_lib.load().ptmi_scene_check(v), 'ptmi_scene_check')
 

@@ -243,6 +243,8 @@ class DeviceLayout:
 
     # internal nodes (the node array may hold unused padding rows besides)
     n_internal: int = None
+    # enclosing medium shell hint (include/ptmi.h `shell`, find_shell), 0 = none
+    shell: int = 0
 
     @property
     def n_inner(self):
@@ -357,6 +359,39 @@ def node_slots(left, right, is_leaf):
     return slot, int(idx.shape[0])
 
 
+def find_shell(sa: SceneArrays, max_leaf_depth: int):
+    """The scene's enclosing medium shell (include/ptmi.h, ``shell``), as the
+    reference BVH node index of its leaf, or -1: a constant-medium sphere of
+    finite radius R > 0 whose leaf is not the root, with the farthest corner of
+    every other leaf's box within R / 2 of its centre (float64), in a BVH of
+    leaf depth <= 62. Of several, the largest. The "final scene" global fog
+    (vol2: constant_medium(Sphere((0, 0, 0), 5000), 0.0001), the rest within
+    0.2835 R) is one; a ray that starts within R / 2 of the centre and reaches
+    the shell, or leaves it outwards, can hit nothing else on the way."""
+    b = sa.bvh
+    ptype, pidx = b['bvh_prim_type'], b['bvh_prim_idx']
+    n = ptype.shape[0]
+    if n < 3 or max_leaf_depth > 62:
+        return -1
+    leaves = np.nonzero(pidx >= 0)[0]
+    bmin = b['bvh_bbox_min'][leaves].astype(np.float64)
+    bmax = b['bvh_bbox_max'][leaves].astype(np.float64)
+    med = np.asarray(sa.sphere_mats['is_constant_medium']) > 0
+    best, best_r = -1, 0.0
+    for k, node in enumerate(leaves):
+        if node == 0 or ptype[node] != PRIM_SPHERE or not med[pidx[node]]:
+            continue
+        c = sa.sphere_data[pidx[node], :3].astype(np.float64)
+        r = float(sa.sphere_data[pidx[node], 3])
+        if not (np.isfinite(r) and r > 0.0 and np.all(np.isfinite(c))):
+            continue
+        far = np.sqrt(np.sum(np.maximum(np.abs(bmin - c), np.abs(bmax - c)) ** 2, axis=1))
+        far[k] = 0.0
+        if np.all(far <= 0.5 * r) and r > best_r:
+            best, best_r = int(node), r
+    return best
+
+
 def pack_device(sa: SceneArrays, node_bytes: int = NODE_BYTES, leaf_order: bool = True) -> DeviceLayout:
     """Reference-layout arrays -> include/ptmi.h device layout. ``node_bytes``
     is the library's node stride (ptmi_node_bytes(): 80, one child record
@@ -431,7 +466,12 @@ def pack_device(sa: SceneArrays, node_bytes: int = NODE_BYTES, leaf_order: bool 
         max_leaf_depth = int(leaf_depths(b).max())
     else:
         root_ref, root_min, root_max, max_leaf_depth = 0, np.zeros(3, np.float32), np.zeros(3, np.float32), 0
-    spheres = np.ascontiguousarray(np.asarray(sa.sphere_data, np.float32).reshape(ns, 4)[ps])
+    # shell hint: 1 + byte offset of the node holding the shell's leaf as a child + the child index
+    shell, leaf = 0, find_shell(sa, max_leaf_depth)
+    if leaf > 0:
+        par = int(b['bvh_parent'][leaf])
+        shell = 1 + int(cidx[par]) * node_bytes + (0 if int(left[par]) == leaf else 1)
+    spheres =np.ascontiguousarray(np.asarray(sa.sphere_data, np.float32).reshape(ns, 4)[ps])
     q = sa.quads
     quads = np.zeros((nq, 16), np.float32)
     quads[:, 0:3] = q['quad_normal']
@@ -467,7 +507,7 @@ def pack_device(sa: SceneArrays, node_bytes: int = NODE_BYTES, leaf_order: bool 
     if pperm.min() < 0 or pperm.max() > 255:
         raise ValueError('Perlin permutation out of range')
     return DeviceLayout(nodes, root_ref, root_min, root_max, max_leaf_depth, spheres, quads, tris, mats,
-                        texels, offs, ws, hs, pv, pperm, ns, nq, nt, perm, ref_nodes, int(internal.shape[0]))
+                        texels, offs, ws, hs, pv, pperm, ns, nq, nt, perm, ref_nodes, int(internal.shape[0]), shell)
 
 
 def compile_world(world, perlin_tables=None):
