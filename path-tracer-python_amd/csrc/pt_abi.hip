@@ -242,7 +242,7 @@ static int check_workspace(const void* ws, size_t bytes, size_t need, bool batch
 }
 
 static bool bad_tile_count(int32_t n_tiles, const DevFrame& fr) {
-  return n_tiles < 0 || (int64_t)n_tiles > mk_tile_count(fr);
+  return n_tiles < 0 || n_tiles > tile_grid(fr).ntiles;
 }
 
 // One thread per element in grid-stride loops: at most 4096 blocks.
@@ -268,7 +268,7 @@ static int render_ws_any(const char* what, RenderKind kind, const ptmi_scene_vie
   if (s_begin < 0 || s_count < 0) return fail(PTMI_EINVAL, "bad sample range");
   const int32_t npix = fr.w * fr.n_rows;
   if (npix == 0) return PTMI_OK;
-  const size_t need = kind == kMkStaged ? mk_workspace_bytes(npix, 1) : wf_workspace_bytes(npix, 1);
+  const size_t need = kind == kMkStaged ? mk_workspace_bytes(npix, 1) : wf_workspace_bytes(fr, 1);
   if (int rc = check_workspace(ws, ws_bytes, need, false)) return rc;
   if (s_count == 0) return PTMI_OK;
   unsigned long long* cnt = (unsigned long long*)counters;
@@ -288,7 +288,7 @@ static int mk_trace_any(const char* what, bool listed, const ptmi_scene_view* sc
   if (int rc = to_dev(scene, frame, sc, fr)) return rc;
   if (s_begin < 0 || s_count < 1) return fail(PTMI_EINVAL, "bad sample range");
   if (listed && bad_tile_count(n_tiles, fr))
-    return fail(PTMI_EINVAL, "n_tiles %d outside [0, %lld]", n_tiles, (long long)mk_tile_count(fr));
+    return fail(PTMI_EINVAL, "n_tiles %d outside [0, %lld]", n_tiles, (long long)tile_grid(fr).ntiles);
   if (listed && n_tiles > 0 && (!tile_list || !aligned4(tile_list)))
     return fail(PTMI_EINVAL, "tile_list NULL/misaligned");
   const int32_t npix = fr.w * fr.n_rows;
@@ -314,7 +314,7 @@ static int mk_resolve_any(const char* what, bool with_stats, const ptmi_frame* f
   if (s_count < 1) return fail(PTMI_EINVAL, "sample_count must be >= 1");
   if (tile_list && (!aligned4(tile_list) || bad_tile_count(n_tiles, fr)))
     return fail(PTMI_EINVAL, "tile_list misaligned or n_tiles %d outside [0, %lld]", n_tiles,
-                (long long)mk_tile_count(fr));
+                (long long)tile_grid(fr).ntiles);
   const int32_t npix = fr.w * fr.n_rows;
   if (npix == 0) return PTMI_OK;
   if (int rc = check_workspace(ws, ws_bytes, mk_workspace_bytes(npix, s_count), true)) return rc;
@@ -431,7 +431,7 @@ size_t ptmi_wf_workspace_bytes(const ptmi_frame* frame, int32_t batch_samples) {
     fail(PTMI_ECAPACITY, "pixels x batch_samples exceeds 2^31 work items");
     return 0;
   }
-  return wf_workspace_bytes(fr.w * fr.n_rows, batch_samples);
+  return wf_workspace_bytes(fr, batch_samples);
 }
 
 int ptmi_wf_render(const ptmi_scene_view* scene, const ptmi_frame* frame, void* workspace, size_t workspace_bytes,
@@ -456,7 +456,11 @@ int ptmi_mk_tile_grid(const ptmi_frame* frame, int32_t* tile_w, int32_t* tile_h,
   DevFrame fr;
   if (int rc = to_dev_frame(frame, fr)) return rc;
   if (!tile_w || !tile_h || !tiles_x || !tiles_y) return fail(PTMI_EINVAL, "tile grid output is NULL");
-  mk_tile_grid(fr, tile_w, tile_h, tiles_x, tiles_y);
+  const TileGrid g = tile_grid(fr);
+  *tile_w = 1 << g.tw_log2;
+  *tile_h = 64 >> g.tw_log2;
+  *tiles_x = g.tiles_x;
+  *tiles_y = g.tiles_x > 0 ? g.ntiles / g.tiles_x : 0;
   return PTMI_OK;
 }
 

@@ -18,22 +18,6 @@
 
 namespace ptmi {
 
-// The frame's megakernel tiles (mk_tile_grid) as the kernels here need them.
-struct TileGrid {
-  int32_t tw_log2;  // tile width log2 (3: 8x8, 4: 16x4, 5: 32x2, 6: 64x1)
-  int32_t tiles_x, ntiles;
-};
-
-static TileGrid tile_grid(const DevFrame& fr) {
-  int32_t tw = 0, th = 0, tx = 0, ty = 0;
-  mk_tile_grid(fr, &tw, &th, &tx, &ty);
-  TileGrid g;
-  g.tw_log2 = tw == 8 ? 3 : tw == 16 ? 4 : tw == 32 ? 5 : 6;
-  g.tiles_x = tx;
-  g.ntiles = tx * ty;
-  return g;
-}
-
 // Lane p of tile t -> the pixel's column in the window and its local row (as
 // bind() of mk_render_kernel); false outside the frame.
 __device__ __forceinline__ bool tile_pixel(const DevFrame& fr, const TileGrid& g, int32_t t, int32_t p, int32_t& col,
@@ -189,7 +173,5 @@ hipError_t launch_tile_update(const DevFrame& fr, const float* stats, float thre
   hipLaunchKernelGGL(tile_compact, dim3(1), dim3(kScanBlock), 0, stream, tile_state, g.ntiles, tile_list, n_active);
   return hipGetLastError();
 }
-
-int64_t mk_tile_count(const DevFrame& fr) { return tile_grid(fr).ntiles; }
 
 }  // namespace ptmi

@@ -28,7 +28,7 @@ constexpr int kNumCounters = PTMI_NUM_COUNTERS;  // include/ptmi.h
 // exact arithmetic; the 64-bit product n * m does not wrap while n < 2^31
 // (any n < 2^32 when d is a power of two, m = 2^32 + 1). Callers keep n below
 // 2^31: the megakernel divides unit ids (item >> 6), the wavefront padded work
-// item ids, bounded in wf_render.
+// item ids, bounded by wf_max_batch (pt_wf_plan.hpp).
 struct FastDiv {
   uint64_t m;
   uint32_t sh, d;

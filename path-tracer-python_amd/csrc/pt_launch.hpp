@@ -9,8 +9,27 @@
 #include <type_traits>
 
 #include "pt_device.hpp"
+#include "pt_mk_plan.hpp"
+#include "pt_wf_plan.hpp"
 
 namespace ptmi {
+// Where a launch's shape is decided: pt_mk_plan.hpp and pt_wf_plan.hpp (tile
+// grid, workspace layouts, id limits, grids; mk_workspace_bytes, mk_max_batch,
+// wf_workspace_bytes and tile_grid come from there), checked on the CPU by
+// plan_check.cpp.
+//
+// The samples per batch of a render of s_count samples: at most max_batch (the
+// integrator's id limit), halved until bytes_of_batch(batch) fits ws_bytes;
+// 0 if not even one sample does.
+template <class F>
+int32_t fit_batch(int32_t s_count, int64_t max_batch, F&& bytes_of_batch, size_t ws_bytes) {
+  int32_t batch = s_count;
+  if (batch > max_batch) batch = (int32_t)max_batch;
+  if (batch < 1) return 0;
+  while (batch > 1 && bytes_of_batch(batch) > ws_bytes) batch = (batch + 1) / 2;
+  return bytes_of_batch(batch) > ws_bytes ? 0 : batch;
+}
+
 // The one traversal dispatch of the library: (frame.traversal, stack slots
 // needed = max_leaf_depth + 1) to a kernel's compile-time (STACK, TRAV),
 // handed to f as two std::integral_constant<int, .> arguments. Stackless
@@ -44,7 +63,6 @@ hipError_t mk_render(const DevScene& sc, const DevFrame& fr, int32_t stack_neede
                      int32_t s_begin, int32_t s_count, unsigned long long* counters, hipStream_t stream);
 // Megakernel over (tile, sample chunk) work units, colours staged per
 // (sample, pixel) and resolved in sample order.
-size_t mk_workspace_bytes(int32_t npix, int32_t batch);
 hipError_t mk_render_staged(const DevScene& sc, const DevFrame& fr, int32_t stack_needed, void* ws,
                             size_t ws_bytes, float* accum, int32_t s_begin, int32_t s_count,
                             unsigned long long* counters, hipStream_t stream);
@@ -56,22 +74,18 @@ hipError_t mk_render_staged(const DevScene& sc, const DevFrame& fr, int32_t stac
 hipError_t mk_trace_staged(const DevScene& sc, const DevFrame& fr, int32_t stack_needed, void* ws,
                            const int32_t* tile_list, int32_t n, int32_t s_begin, int32_t nb,
                            unsigned long long* counters, hipStream_t stream);
-int64_t mk_max_batch(const DevFrame& fr);
 // stats != nullptr: every batch resolves through launch_stats_resolve.
 hipError_t wf_render(const DevScene& sc, const DevFrame& fr, int32_t stack_needed, void* ws, size_t ws_bytes,
                      float* accum, int32_t s_begin, int32_t s_count, unsigned long long* counters,
                      hipStream_t stream, float* stats = nullptr);
-size_t wf_workspace_bytes(int32_t npix, int32_t batch);
 // Sets the wavefront tail threshold (capacity / divisor; 0 = no tail launch); returns the previous one.
 int32_t wf_set_drain_at(int32_t divisor);
 // accum[pixel] += staging[s][p] for s = 0..batch-1 in order (profiled as `prof_kind`).
 hipError_t launch_stage_resolve(const DevFrame& fr, const float* staging, int32_t npix, int32_t batch,
                                 float* accum, int prof_kind, hipStream_t stream);
 
-// Adaptive sampling (pt_adaptive.hip; the listed trace is pt_megakernel.hip's).
-// The staged megakernel's 64-pixel tiles of a frame: tile size and grid.
-void mk_tile_grid(const DevFrame& fr, int32_t* tile_w, int32_t* tile_h, int32_t* tiles_x, int32_t* tiles_y);
-int64_t mk_tile_count(const DevFrame& fr);
+// Adaptive sampling (pt_adaptive.hip; the listed trace is pt_megakernel.hip's),
+// over the staged megakernel's 64-pixel tiles (tile_grid, pt_mk_plan.hpp).
 // launch_stage_resolve plus the Welford update of stats[pixel] = {n, mean, M2, 0};
 // tile_list == nullptr: every pixel of the frame, else the pixels of the listed tiles.
 hipError_t launch_stats_resolve(const DevFrame& fr, const float* staging, int32_t npix, int32_t batch, float* accum,

@@ -159,99 +159,9 @@ __device__ __forceinline__ void start_path(const DevFrame& fr, int32_t px, int32
 // over 4-wave 16x16 blocks: a finished wave frees its slot at once).
 constexpr int kMkBlock = 64;
 
-// Staged mode, persistent waves: the grid is one round of the chip's wave
-// slots and every wave draws 64-item units (one 8x8 tile x one sample) from a
-// device counter and refills its lanes across units — no wave ends while work
-// is left, and there is no partly empty last round. Units are tile-major (all
-// samples of a tile are consecutive), and a fetch takes up to
-// PTMI_MK_CHUNK_SAMPLES units while plenty are left, fewer in the tail, so a
-// wave changes tile rarely (lanes of two tiles in one wave fetch more distinct
-// cache lines per load) and the last fetches are small.
-#ifndef PTMI_MK_CHUNK_SAMPLES
-#define PTMI_MK_CHUNK_SAMPLES 32  // A/B (C2, C4): 32/4 ~ 16/4 ~ 64/4 > 16/2, 16/8, 8/4 >> 64/2
-#endif
-#ifndef PTMI_MK_TAIL_DIV_SMALL
-#define PTMI_MK_TAIL_DIV_SMALL 2  // ... for batches of fewer than PTMI_MK_SMALL_BATCH samples
-#endif
-#ifndef PTMI_MK_SMALL_BATCH
-#define PTMI_MK_SMALL_BATCH 8000000
-#endif
-#ifndef PTMI_MK_SMALL_WPC
-// Persistent waves per CU for a batch of fewer than PTMI_MK_SMALL_GRID_BATCH
-// samples (the occupancy allows 20 for vol2): the next overlapped call's waves
-// share the chip while this one drains. A/B on MI355X, an 8-rank tile shard's
-// 64-spp calls against 20 waves per CU: 10 +1.1 %, 12 +0.6 %, 14 +0.5 %, 16
-// -0.6 %, 8 -4 %, 6 -29 % (profiles/r06/ab/mk_small_grid.log; round 5:
-// profiles/r05/ab/ab_mk_persist_wpc.log).
-#define PTMI_MK_SMALL_WPC 10
-#endif
-#ifndef PTMI_MK_SMALL_GRID_BATCH
-// Batches (samples) below which PTMI_MK_SMALL_WPC applies: 16 M covers the
-// 4-rank tile shard (10.2 M samples per 64-spp call: +0.7 % over the full
-// grid) and leaves 2-rank shards (20.5 M) and whole frames on the full grid
-// (profiles/r06/ab/mk_small_grid.log).
-#define PTMI_MK_SMALL_GRID_BATCH 16000000
-#endif
-#ifndef PTMI_MK_TAIL_DIV
-#define PTMI_MK_TAIL_DIV 4  // a fetch takes at most (units left) / (TAIL_DIV * waves) units
-                            // (re-tuned: 2 is +3 % on C2 but -8 % on C4's long fog paths;
-                            // profiles/r01/ab_fetch_sizing.log)
-#endif
-
-// Unit counters: the units are split into PTMI_MK_SHARDS contiguous shards,
-// each with its own counter on its own 256-B line, and wave w pulls from shard
-// w % PTMI_MK_SHARDS first (one shard per XCD under round-robin placement),
-// then steals from the others. One device-scope counter saturates near 88
-// returning atomics per us (MI355X_MICROARCH.md, "dequeue"), and a launch
-// makes ~10^5 fetches, most of them small ones in its tail, where every wave
-// is waiting for its next unit.
-#ifndef PTMI_MK_SHARDS
-#define PTMI_MK_SHARDS 8
-#endif
-// Shard s holds tiles s, s + S, s + 2S, ... (interleaved across the image, so
-// every shard costs about the same; 0: contiguous unit ranges, whose shards
-// drain at different times). A/B on MI355X, C2, 64-spp calls (overlapped):
-// one counter 2448 (2479), 8 contiguous shards 2320 (2546), 8 interleaved
-// 2560 (2597), 4 interleaved 2552 (2590) Msamples/s; 16-spp calls 1954 ->
-// 2324 (profiles/r02/ab/ab_mk_shards.log).
-constexpr int kMkShards = PTMI_MK_SHARDS;
-constexpr int kMkCtlLine = 64;  // int32 words per 256-B counter line
-
-struct MkWork {
-  int32_t* ctl;      // kMkShards counters, one per 256-B line: units taken from each shard (zeroed before the launch)
-  int32_t shard_len; // units per shard (the last one may be short)
-  int32_t csamp;     // most units per fetch
-  int32_t tiles_x;   // 64-pixel tiles per row
-  int32_t tw_log2;   // tile width log2: 3 for 8x8 tiles, 4 for 16x4, 5 for 32x2, 6 for 64x1
-  int32_t nb;        // samples of the batch (units per tile)
-  FastDiv by_nb, by_tiles_x, by_len;
-  int32_t nunits;    // units of the batch (multiple of csamp)
-  int32_t tail_div;  // TAIL_DIV * waves of the grid
-  // tile-listed launches (mk_render_kernel's LISTED): the batch's virtual tile
-  // v is tile tile_list[v]; v >= n_list or an id outside [0, ntiles) decodes
-  // outside the frame, as the shards' padded units do
-  const int32_t* tile_list;
-  int32_t n_list, ntiles;
-};
+// The staged mode's persistent waves, its work units and their shards: MkWork and
+// the tuning constants of its launch shape are in pt_mk_plan.hpp.
 constexpr int kMkTile = 8;
-
-// Tile height (log2) of the staged megakernel's 64-pixel tiles. A frame's
-// local rows are its row bands packed together, so an 8x8 tile over 4-row
-// bands (bench.py --gpus 8 at 800 rows) would cover two runs of 4 image rows
-// 32 rows apart; a tile as tall as the band's largest power-of-two divisor
-// (16x4, 32x2, 64x1) stays inside one band. Which lane renders which pixel
-// changes nothing in the image (staging[sample][pixel], ordered resolve).
-static int mk_tile_rows_log2(const DevFrame& fr) {
-  if (fr.band_stride <= 1) return 3;
-  const int32_t th = fr.band_rows & -fr.band_rows;
-  return th >= 8 ? 3 : th >= 4 ? 2 : th >= 2 ? 1 : 0;
-}
-static int64_t mk_tiles(const DevFrame& fr, int32_t* tx_out = nullptr) {
-  const int hl = mk_tile_rows_log2(fr), tw = 64 >> hl, th = 1 << hl;
-  const int64_t tx = (fr.w + tw - 1) / tw, ty = (fr.n_rows + th - 1) / th;
-  if (tx_out) *tx_out = (int32_t)tx;
-  return tx * ty;
-}
 
 template <int STACK, bool STAGED, int TRAV = PTMI_TRAV_STACK, bool LISTED = false, bool SHELL = false>
 // waves/SIMD the LDS stack allows: 160 KiB / (STACK * 8 B * 256) blocks per CU
@@ -819,15 +729,6 @@ hipError_t mk_render(const DevScene& sc, const DevFrame& fr, int32_t stack_neede
 }
 
 // ---------------------------------------------------------------- staged
-static size_t mk_staging_bytes(int32_t npix, int32_t batch) {
-  return (3 * sizeof(float) * (size_t)npix * (size_t)batch + 255) & ~(size_t)255;
-}
-
-size_t mk_workspace_bytes(int32_t npix, int32_t batch) {  // staging + the shards' 256-B counter lines
-  if (npix <= 0 || batch <= 0) return 0;
-  return mk_staging_bytes(npix, batch) + 256 * kMkShards;
-}
-
 // The megakernel of one staged batch: every (sample, pixel) colour of the
 // batch into staging[sample][pixel]; the accumulator is not touched (the
 // resolve is launch_stage_resolve, on the caller's schedule).
@@ -838,53 +739,19 @@ static hipError_t launch_mk_trace(const DevScene& sc, const DevFrame& fr, float*
                                   int32_t nb, unsigned long long* counters, hipStream_t stream,
                                   const int32_t* tile_list, int32_t n_list) {
   float* accum = nullptr;  // staged kernels write staging only
-  int32_t tx = 0;
-  const int64_t frame_tiles = mk_tiles(fr, &tx);
-  const int64_t tiles = LISTED ? (int64_t)n_list : frame_tiles;  // tiles the units cover
-  const int64_t batch_samples = (LISTED ? 64 * tiles : (int64_t)fr.w * fr.n_rows) * nb;
   int dev = 0, ncu = 0, per_cu = 0;
   hipError_t e0 = hipGetDevice(&dev);
   if (e0 == hipSuccess) e0 = hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
   if (e0 == hipSuccess)
     e0 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, mk_render_kernel<STACK, true, TRAV, LISTED, SHELL>, kMkBlock, 0);
   if (e0 != hipSuccess) return e0;
-  MkWork wk;
-  wk.ctl = (int32_t*)((char*)staging + mk_staging_bytes(fr.w * fr.n_rows, nb));
-  wk.csamp = PTMI_MK_CHUNK_SAMPLES;
-  wk.tiles_x = tx;
-  wk.tw_log2 = 6 - mk_tile_rows_log2(fr);
-  wk.nb = nb;
-  wk.tile_list = tile_list;
-  wk.n_list = n_list;
-  wk.ntiles = (int32_t)frame_tiles;
-  if (tiles * nb * 64 >= (1ll << 32)) return hipErrorInvalidValue;  // item ids are 32-bit
-  // shard s: tiles s, s + S, ... (interleaved across the image, so every shard
-  // costs about the same); virtual units past the last tile decode to rows
-  // outside the frame and are skipped
-  wk.shard_len = (int32_t)((tiles + kMkShards - 1) / kMkShards) * nb;
-  wk.nunits = wk.shard_len * kMkShards;
-  if ((int64_t)wk.nunits * 64 >= (1ll << 32)) return hipErrorInvalidValue;
-  wk.by_len = fast_div((uint32_t)wk.shard_len);
-  wk.by_nb = fast_div((uint32_t)nb);
-  wk.by_tiles_x = fast_div((uint32_t)wk.tiles_x);
-  // Small batches (an 8-rank tile shard) run on a smaller persistent grid, so
-  // the next overlapped call's waves share the chip while this one drains.
-  if (batch_samples < PTMI_MK_SMALL_GRID_BATCH && per_cu > PTMI_MK_SMALL_WPC) per_cu = PTMI_MK_SMALL_WPC;
-  int64_t waves = (int64_t)(per_cu > 0 ? per_cu : 1) * (ncu > 0 ? ncu : 1);
-  const int64_t chunks = wk.nunits;
-  if (waves > chunks) waves = chunks;
-  // per shard: the waves pulling from it. Small batches (a multi-GPU tile
-  // shard: 5 M samples per call for vol2 at 8 GPUs) are all tail: halving the
-  // divisor there takes larger fetches, so a wave changes tile less often
-  // (A/B, 8-rank rehearsal: +2 % per GPU; profiles/r03/ab/ab_mk_small_calls.log).
-  const int64_t tail = batch_samples < PTMI_MK_SMALL_BATCH ? PTMI_MK_TAIL_DIV_SMALL : PTMI_MK_TAIL_DIV;
-  const int64_t tdiv = tail * waves / kMkShards;
-  wk.tail_div = (int32_t)(tdiv > 1 ? tdiv : 1);
-  e0 = hipMemsetAsync(wk.ctl, 0, 256 * kMkShards, stream);
+  const MkPlan plan = mk_plan(fr, staging, nb, tile_list, n_list, per_cu, ncu);
+  if (plan.err != hipSuccess) return plan.err;  // item ids are 32-bit
+  e0 = hipMemsetAsync(plan.wk.ctl, 0, plan.ctl_bytes, stream);
   if (e0 != hipSuccess) return e0;  // never launch on stale work counters
   const int pslot = prof_begin(kProfMk, stream);
-  hipLaunchKernelGGL((mk_render_kernel<STACK, true, TRAV, LISTED, SHELL>), dim3((unsigned)waves), dim3(kMkBlock), 0, stream,
-                     sc, fr, accum, s_begin, nb, nb, staging, counters, wk);
+  hipLaunchKernelGGL((mk_render_kernel<STACK, true, TRAV, LISTED, SHELL>), dim3(plan.waves), dim3(kMkBlock), 0, stream,
+                     sc, fr, accum, s_begin, nb, nb, staging, counters, plan.wk);
   prof_end(pslot, stream);
   return hipGetLastError();
 }
@@ -913,35 +780,15 @@ hipError_t mk_trace_staged(const DevScene& sc, const DevFrame& fr, int32_t stack
   return trace(std::true_type{}, std::true_type{});
 }
 
-void mk_tile_grid(const DevFrame& fr, int32_t* tile_w, int32_t* tile_h, int32_t* tiles_x, int32_t* tiles_y) {
-  const int hl = mk_tile_rows_log2(fr);
-  int32_t tx = 0;
-  const int64_t tiles = mk_tiles(fr, &tx);
-  *tile_w = 64 >> hl;
-  *tile_h = 1 << hl;
-  *tiles_x = tx;
-  *tiles_y = tx > 0 ? (int32_t)(tiles / tx) : 0;
-}
-
-int64_t mk_max_batch(const DevFrame& fr) {
-  // item ids (tile, sample, pixel of the 64-pixel tile) are 32-bit: tiles * batch * 64 < 2^32
-  const int64_t tiles = mk_tiles(fr);
-  const int64_t padded = (tiles + kMkShards - 1) / kMkShards * kMkShards;  // interleaved shards' virtual units
-  return tiles > 0 ? ((1ll << 32) - 1) / (padded * 64) : 0;
-}
-
 hipError_t mk_render_staged(const DevScene& sc, const DevFrame& fr, int32_t stack_needed, void* ws,
                             size_t ws_bytes, float* accum, int32_t s_begin, int32_t s_count,
                             unsigned long long* counters, hipStream_t stream) {
   if (s_count < 2)  // one sample: direct accumulation, no staging
     return mk_render(sc, fr, stack_needed, accum, s_begin, s_count, counters, stream);
   const int32_t npix = fr.w * fr.n_rows;
-  int32_t batch = s_count;
-  const int64_t max_batch = mk_max_batch(fr);
-  if (max_batch < 1) return hipErrorInvalidValue;
-  if (batch > max_batch) batch = (int32_t)max_batch;
-  while (batch > 1 && mk_workspace_bytes(npix, batch) > ws_bytes) batch = (batch + 1) / 2;
-  if (mk_workspace_bytes(npix, batch) > ws_bytes) return hipErrorInvalidValue;
+  const int32_t batch =
+      fit_batch(s_count, mk_max_batch(fr), [&](int32_t b) { return mk_workspace_bytes(npix, b); }, ws_bytes);
+  if (batch < 1) return hipErrorInvalidValue;
   for (int32_t b0 = 0; b0 < s_count; b0 += batch) {
     const int32_t nb = s_count - b0 < batch ? s_count - b0 : batch;
     hipError_t e = mk_trace_staged(sc, fr, stack_needed, ws, nullptr, 0, s_begin + b0, nb, counters, stream);

@@ -83,31 +83,9 @@
 
 namespace ptmi {
 
-constexpr int kShards = 8;
-#ifndef PTMI_WF_CHUNK_SAMPLES
-#define PTMI_WF_CHUNK_SAMPLES 4  // samples per work chunk (one 8x8 pixel square each)
-#endif
-#ifndef PTMI_WF_BLOCK
-#define PTMI_WF_BLOCK 128  // threads per block of the queue kernels (A/B on MI355X, parity-identical: 128 vs 256
-                           // C3 +1.2 %, mesh fog +1.7 %; 64: C3 -6 %, mesh fog +2.3 %; profiles/r02/ab/ab_wf_block.log)
-#endif
-constexpr int kWfBlock = PTMI_WF_BLOCK;
-#ifndef PTMI_WF_ISECT_LDS
-// Stack slots wf_intersect keeps in LDS when its stack is deeper than 16
-// slots; the deeper slots spill to global memory (Stack, pt_device.hpp). Its
-// LDS stacks set its occupancy: the 20-slot kernel (leaf depth 16-19, e.g.
-// the mesh-fog torus) fits 4 waves/SIMD with all slots in LDS, 7 with 11
-// (67 VGPRs). A/B on MI355X, parity-identical (also with 3 LDS slots, where
-// most pushes spill): mesh fog +2.2 %; for the 16-slot kernel (vol2, C3) 7
-// waves measured -1.5 % on round 3's in-place slots (profiles/r03/ab/ab_wf_spill.log)
-// and +0.8 % on round 5's compacted buffers (PTMI_WF_SPILL_MIN_STACK below). A
-// 16-slot wf_intersect padded down to 4 waves/SIMD loses 8 % (3 waves: 18 %).
-#define PTMI_WF_ISECT_LDS 10
-#endif
-#ifndef PTMI_WF_SPILL_MAX_STACK
-#define PTMI_WF_SPILL_MAX_STACK 20  // kernels of 17 to this many stack slots spill; deeper ones keep them all in LDS
-#endif
-constexpr int kSpillSlots = PTMI_WF_SPILL_MAX_STACK > PTMI_WF_ISECT_LDS ? PTMI_WF_SPILL_MAX_STACK - PTMI_WF_ISECT_LDS : 0;
+// The buffers (RayBuf, WfBufs), the pipes, the counter lines and the constants
+// that size them (PTMI_WF_ISECT_LDS, the LDS stack slots of a spilling
+// wf_intersect, among them) are in pt_wf_plan.hpp.
 #ifndef PTMI_WF_SPILL_MIN_STACK
 // Kernels of this many stack slots up to PTMI_WF_SPILL_MAX_STACK spill. Round 5,
 // on the compacted buffers: the 16-slot kernel (vol2) with 11 slots in LDS and
@@ -124,8 +102,8 @@ constexpr int isect_lds() {
              ? PTMI_WF_ISECT_LDS
              : STACK;
 }
-// ... and with 10 LDS slots (10 KiB per 2-wave block: 8 waves/SIMD) the
-// kernel is held to the 8-wave VGPR budget (64 VGPRs; 100 B/lane of scratch
+// With PTMI_WF_ISECT_LDS = 10 LDS slots (10 KiB per 2-wave block: 8 waves/SIMD)
+// the kernel is held to the 8-wave VGPR budget (64 VGPRs; 100 B/lane of scratch
 // instead of 52): A/B on MI355X, parity-identical, against 11 slots at 7 waves
 // (70 VGPRs): C3 +1.5 % (bench.py 2033 vs 2003), mesh fog +0.7 %
 // (profiles/r05/ab/ab_wf_isect_8waves.log). Kernels that keep more slots in
@@ -137,93 +115,13 @@ template <int STACK, int TRAV>
 constexpr int isect_min_waves() {
   return (isect_lds<STACK, TRAV>() < STACK && isect_lds<STACK, TRAV>() <= 10) ? PTMI_WF_ISECT_MIN_WAVES : 1;
 }
-#ifndef PTMI_WF_MAX_BLOCKS
-#define PTMI_WF_MAX_BLOCKS (2048 * 256 / PTMI_WF_BLOCK)  // all pipes together; A/B: 4096 -1.5 %, 8192 -3.5 % (C3)
-#endif
 // A fresh camera ray (generated and traced in this iteration's wf_intersect)
 // is stored as its item | kFresh and nothing else: wf_scatter regenerates it
 // from the item (get_ray, kernels.py:176-201: the same draws from the same
 // counter-based stream), with throughput 1 and depth 0. Items are < 2^31
-// (wf_render bounds them).
+// (wf_max_batch, pt_wf_plan.hpp).
 constexpr uint32_t kFresh = 0x80000000u;
 
-// Continuing-ray segments: kBins direction bins x kShards producer shards,
-// one counter each (kSegs <= 64: one wave holds them all, one per lane).
-// Sorting by octant, A/B on MI355X (round 5, parity-identical;
-// profiles/r05/ab/ab_wf_sort.log): against the round-4 in-place slots
-// (1685-1694 Msamples/s on C3, 705-708 on mesh fog) the compacted buffers
-// alone (one bin) give 1889-1900 / 847-849, sorted by octant 1914-1923 /
-// 850-854; wf_intersect's lane efficiency 0.43 unsorted, 0.45 sorted.
-constexpr int kBins = 8;
-constexpr int kSegs = kBins * kShards;
-#ifndef PTMI_WF_SEG_DIV
-#define PTMI_WF_SEG_DIV 16  // a segment's region holds capacity / this rays (4x an even share of 64 segments)
-#endif
-
-// Ray buffer of one iteration parity: positions [0, npos) of six streams.
-// Segment s holds positions [s * seg_cap, (s + 1) * seg_cap), the overflow
-// region the next `capacity`, the fresh camera rays the last `capacity`.
-struct RayBuf {
-  float4* a;       // o.xyz, d.x
-  float4* c;       // thr.xyz, meta (bits)
-  float2* d;       // d.y, d.z
-  float2* hit;     // t, leaf ref (bits) of the closest hit (wf_intersect -> wf_scatter)
-  uint32_t* item;  // work item (| kFresh)
-  uint32_t* ctr;   // rng draw counter
-};
-
-// Closest-hit lists (wf_intersect fills them, wf_scatter drains them).
-// Each list holds kShards segments of medseg ray positions; the medium and
-// Perlin lists share one array, the Perlin one filling its segments from the
-// top (a ray is in at most one list, so together they never exceed a segment).
-// Misses and emissive hits (class kListEnded) end in wf_intersect: a lane
-// that finishes its traversal early ends its path while the wave's longest
-// traversal runs, nearly for free. A/B on MI355X (round 4): an ended list
-// drained by wf_scatter instead cost wf_scatter +19 % for wf_intersect -2.4 %,
-// C3 -5 % (profiles/r04/ab/). kListEnded is a class, not a list.
-enum : int32_t { kListLambertian = 0, kListGlossy = 1, kListDielectric = 2, kListMedium = 3, kListNoise = 4,
-                 kListEnded = 5, kLists = 5 };
-
-struct WfBufs {
-  RayBuf rb[2];       // by iteration parity: wf_intersect(k) and wf_scatter(k) read rb[k & 1], wf_scatter(k) writes rb[(k + 1) & 1]
-  int32_t* lists;     // 4 arrays of kShards x medseg positions: Lambertian, glossy, dielectric, medium + Perlin
-  float* staging;     // [batch][npix][3] path colours
-  int32_t* ctl;       // this pipe's counters, one per 256-B line (see ctl_*)
-  char* spill;        // this pipe's spilled stack slots of wf_intersect (kSpillSlots rows of its grid's threads)
-  int32_t* next;      // next-item counters of the work pool shards, shared by the pipes, one per 256-B line
-  int32_t capacity;   // rays traced per iteration (this pipe)
-  int32_t seg_cap;    // positions per continuing-ray segment
-  int32_t medseg;     // positions per shard segment of a material list
-  int32_t npix;       // pixels of the frame's pixel set
-  int32_t sq_x, nsq;  // 8x8 pixel squares covering the pixel set: per row, total
-  int32_t csamp;      // samples per chunk: a chunk is one square x csamp samples (64 * csamp items)
-  int32_t batch;      // samples of the batch
-  int32_t nitems;     // work items of the batch, padded to whole squares and chunks
-  int32_t shard_len;  // items per pool shard (whole chunks): shard s owns [s*len, min((s+1)*len, nitems))
-  int32_t s_begin;    // first sample of the batch
-  FastDiv by_per, by_nsq, by_sqx;  // item decode: / (64 * csamp), / nsq, / sq_x
-};
-
-// Pipes: the rays are split into PTMI_WF_PIPES independent parts, each
-// driven through its own intersect/scatter loop on its own stream, so one
-// pipe's kernels fill the drain at the end of another's. They share the work
-// pool (next-item counters) and the staging buffer.
-#ifndef PTMI_WF_PIPES
-#define PTMI_WF_PIPES 4  // A/B on MI355X: 1 -> 2 pipes +15 % (C3), 2 -> 4 +5 %
-#endif
-constexpr int32_t kPipes = PTMI_WF_PIPES;
-
-// Device-scope atomics are performed per cache line at the memory side, so
-// counters sharing a line serialize as one: every counter gets its own
-// 256-B line. Lines 0-7: next item per pool shard (shared); then per pipe:
-// its status ([2]: the pool was empty after the last wf_scatter's iteration,
-// written by that wf_scatter; [0], [1]: the continuing rays of the last
-// wf_intersect and the [2] it saw, for the host), two sets (by
-// iteration parity) of kSegs segment counts and one overflow count, and two
-// sets of one count per material list and shard.
-constexpr int32_t kLine = 64;
-constexpr int32_t kPipeLines = 3 + 2 * kSegs + 2 * kLists * kShards;
-constexpr int32_t kCtlWords = (8 + kPipeLines * kPipes) * kLine;
 __host__ __device__ __forceinline__ int32_t* ctl_next(const WfBufs& wb, int32_t s) { return wb.next + s * kLine; }
 __host__ __device__ __forceinline__ int32_t* ctl_status(const WfBufs& wb) { return wb.ctl; }
 __device__ __forceinline__ int32_t* ctl_seg(const WfBufs& wb, int32_t par, int32_t s) {
@@ -1117,72 +1015,19 @@ hipError_t pipe_streams_init(PipeStreams* ps) {
 // drain as soon as the pool is dry).
 #define PTMI_WF_DRAIN_AT 16
 #endif
-#ifndef PTMI_WF_CAPACITY_LOG2
-// rays per iteration (all pipes). A/B: 2^21 +3 % over 2^20 (C3, mesh fog);
-// with the 8-wave wf_intersect (late round 5) 2^22 over 2^21: mesh fog +5 %
-// (two runs), C3 +1.6 % / +-0 (C3 varies +-1.5 %); 2^23: mesh fog +9 %, C3
-// -2 % (profiles/r05/ab/ab_wf_capacity_8waves.log)
-#define PTMI_WF_CAPACITY_LOG2 22
-#endif
-constexpr int32_t kMaxCapacity = 1 << PTMI_WF_CAPACITY_LOG2;
 std::atomic<int32_t> g_drain_at{PTMI_WF_DRAIN_AT};
-constexpr int32_t kSlotQuantum = kShards * kWfBlock;
-
-// per ray position and parity: a 16, c 16, d 8, hit 8, item 4, ctr 4 bytes
-constexpr size_t kPosBytes = 56;
-struct Layout {
-  int32_t capacity, cp, seg_cap, npos, medseg;
-  size_t rb, lists, staging, spill, ctl, total;
-  size_t rb_pipe, lists_pipe;
-};
-constexpr size_t kSpillPipeBytes = (size_t)kSpillSlots * (PTMI_WF_MAX_BLOCKS / kPipes) * kWfBlock * 8;
-
-Layout layout(int32_t npix, int32_t batch) {
-  Layout L;
-  int64_t items = (int64_t)npix * batch;
-  // rays per iteration: 2^22 (or the batch's items if fewer), whatever the
-  // frame size — the pool refills the buffers, so a 4K frame needs no more
-  // (the ray buffers are 56 B x 12 positions per ray: 2.8 GB at 2^22)
-  int64_t cap = kMaxCapacity;
-  if (items < cap) cap = items;
-  cap = (cap + kPipes * kSlotQuantum - 1) / (kPipes * kSlotQuantum) * (kPipes * kSlotQuantum);
-  L.capacity = (int32_t)cap;  // all pipes
-  L.cp = (int32_t)(cap / kPipes);
-  int64_t sc = ((int64_t)L.cp / PTMI_WF_SEG_DIV + 63) / 64 * 64;
-  L.seg_cap = (int32_t)(sc < 64 ? 64 : sc);
-  L.npos = kSegs * L.seg_cap + 2 * L.cp;
-  // a shard's blocks take every kShards-th 128-entry chunk of wf_intersect's
-  // work (<= cp + the bins' and the overflow's padding): a list segment holds them all
-  const int64_t work = (int64_t)L.cp + 64ll * (kBins + 1);
-  const int64_t chunks = (work + kWfBlock - 1) / kWfBlock;
-  L.medseg = (int32_t)((chunks + kShards - 1) / kShards * kWfBlock);
-  L.rb_pipe = 2 * kPosBytes * (size_t)L.npos;
-  L.lists_pipe = 4 * kShards * sizeof(int32_t) * (size_t)L.medseg;
-  L.rb = 0;
-  L.lists = L.rb + kPipes * L.rb_pipe;
-  L.staging = (L.lists + kPipes * L.lists_pipe + 255) & ~(size_t)255;
-  L.spill = (L.staging + 3 * sizeof(float) * (size_t)items + 255) & ~(size_t)255;
-  L.ctl = L.spill + kPipes * kSpillPipeBytes;
-  L.total = L.ctl + kCtlWords * sizeof(int32_t);
-  return L;
-}
 }  // namespace
-
-static_assert((PTMI_WF_MAX_BLOCKS / kPipes) % kShards == 0, "a pipe's grid must be a multiple of the shard count");
 
 // One batch: generate on the caller's stream, fork the pipes, run each pipe's
 // intersect -> scatter loop on its own stream until its rays have all ended
 // and the pool is empty, join, resolve.
 template <int STACK, int TRAV = PTMI_TRAV_STACK>
-static hipError_t wf_batch(const DevScene& sc, const DevFrame& fr, const WfBufs* wbs, float* accum, int32_t batch,
+static hipError_t wf_batch(const DevScene& sc, const DevFrame& fr, const WfPlan& plan, float* accum,
                            unsigned long long* counters, hipStream_t stream, const PipeStreams& ps,
                            float* stats) {
-  // a pipe's grid = a multiple of kShards, so block b's shard is b % kShards
-  int64_t blocks = wbs[0].capacity / kWfBlock;
-  if (blocks > PTMI_WF_MAX_BLOCKS / kPipes) blocks = PTMI_WF_MAX_BLOCKS / kPipes;
-  const unsigned g = (unsigned)blocks;
-  // the tail launch: one lane per continuing ray (<= capacity + the bins' padding)
-  const unsigned gd = (unsigned)((wbs[0].capacity + 64 * (kBins + 1) + kWfBlock - 1) / kWfBlock);
+  const WfBufs* wbs = plan.wb;
+  const int32_t batch = wbs[0].batch;
+  const unsigned g = plan.grid, gd = plan.grid_drain;  // the pipes' iterations; the tail launch
   {  // never launch on stale work counters
     const hipError_t em = hipMemsetAsync(wbs[0].next, 0, kCtlWords * sizeof(int32_t), stream);
     if (em != hipSuccess) return em;
@@ -1200,10 +1045,7 @@ static hipError_t wf_batch(const DevScene& sc, const DevFrame& fr, const WfBufs*
     for (int p = 1; p < kPipes && e == hipSuccess; ++p) e = hipStreamWaitEvent(st[p], ps.fork, 0);
     if (e != hipSuccess) return e;
   }
-  // Each item needs at most max_depth waves and every iteration advances every
-  // live ray by one wave (or starts a new item), so this many iterations
-  // always drain a pipe.
-  const int64_t max_iters = (int64_t)wbs[0].nitems * (int64_t)(fr.max_depth > 0 ? fr.max_depth : 1) + 2;
+  const int64_t max_iters = plan.max_iters;
   bool live[kPipes];
   for (int p = 0; p < kPipes; ++p) live[p] = true;
   int64_t it = 0;
@@ -1320,27 +1162,12 @@ extern "C" int64_t ptmi_wf_trace_read(uint32_t* out, int64_t max_records, int re
 namespace ptmi {
 #endif
 
-size_t wf_workspace_bytes(int32_t npix, int32_t batch) {
-  if (npix <= 0 || batch <= 0) return 0;
-  return layout(npix, batch).total;
-}
-
 hipError_t wf_render(const DevScene& sc, const DevFrame& fr, int32_t stack_needed, void* ws, size_t ws_bytes,
                      float* accum, int32_t s_begin, int32_t s_count, unsigned long long* counters,
                      hipStream_t stream, float* stats) {
-  const int32_t npix = fr.w * fr.n_rows;
-  // work items (sample, pixel) of a batch are ids below 2^31 (FastDiv's
-  // range, and the kFresh bit), padded ids included: 64 per 8x8 pixel square,
-  // and the batch's samples rounded up to whole chunks (wb.nitems below); the
-  // pool counters may run past their shard's end by the lanes asking at once
-  // (< 2^24 in all)
-  const int64_t sq_items = 64ll * ((fr.w + 7) / 8) * ((fr.n_rows + 7) / 8);
-  int32_t batch = s_count;
-  const int64_t max_batch = sq_items > 0 ? (0x7fffffffll - (1ll << 24)) / sq_items - (PTMI_WF_CHUNK_SAMPLES - 1) : 0;
-  if (batch > max_batch) batch = (int32_t)max_batch;
+  const int32_t batch =
+      fit_batch(s_count, wf_max_batch(fr), [&](int32_t b) { return wf_workspace_bytes(fr, b); }, ws_bytes);
   if (batch < 1) return hipErrorInvalidValue;
-  while (batch > 1 && layout(npix, batch).total > ws_bytes) batch = (batch + 1) / 2;
-  if (layout(npix, batch).total > ws_bytes) return hipErrorInvalidValue;
   int dev = 0;
   {
     hipError_t e = hipGetDevice(&dev);
@@ -1355,46 +1182,10 @@ hipError_t wf_render(const DevScene& sc, const DevFrame& fr, int32_t stack_neede
   }
   for (int32_t b0 = 0; b0 < s_count; b0 += batch) {
     const int32_t nb = s_count - b0 < batch ? s_count - b0 : batch;
-    const Layout L = layout(npix, nb);
-    char* base = (char*)ws;
-    const size_t np = (size_t)L.npos;
-    WfBufs wbs[kPipes];
-    for (int p = 0; p < kPipes; ++p) {
-      WfBufs& wb = wbs[p];
-      char* rbp = base + L.rb + p * L.rb_pipe;
-      for (int q = 0; q < 2; ++q) {
-        char* r = rbp + q * kPosBytes * np;
-        wb.rb[q].a = (float4*)r;
-        wb.rb[q].c = (float4*)(r + 16 * np);
-        wb.rb[q].d = (float2*)(r + 32 * np);
-        wb.rb[q].hit = (float2*)(r + 40 * np);
-        wb.rb[q].item = (uint32_t*)(r + 48 * np);
-        wb.rb[q].ctr = (uint32_t*)(r + 52 * np);
-      }
-      wb.lists = (int32_t*)(base + L.lists + p * L.lists_pipe);
-      wb.staging = (float*)(base + L.staging);
-      wb.next = (int32_t*)(base + L.ctl);
-      wb.ctl = wb.next + (8 + p * kPipeLines) * kLine;
-      wb.spill = base + L.spill + p * kSpillPipeBytes;
-      wb.capacity = L.cp;
-      wb.seg_cap = L.seg_cap;
-      wb.medseg = L.medseg;
-      wb.npix = npix;
-      wb.sq_x = (fr.w + 7) / 8;
-      wb.nsq = wb.sq_x * ((fr.n_rows + 7) / 8);
-      wb.batch = nb;
-      wb.csamp = nb < PTMI_WF_CHUNK_SAMPLES ? nb : PTMI_WF_CHUNK_SAMPLES;
-      const int32_t nchunks = wb.nsq * ((nb + wb.csamp - 1) / wb.csamp);
-      wb.nitems = nchunks * 64 * wb.csamp;
-      wb.shard_len = (nchunks + kShards - 1) / kShards * 64 * wb.csamp;
-      wb.s_begin = s_begin + b0;
-      wb.by_per = fast_div(64u * (uint32_t)wb.csamp);
-      wb.by_nsq = fast_div((uint32_t)wb.nsq);
-      wb.by_sqx = fast_div((uint32_t)wb.sq_x);
-    }
+    const WfPlan plan = wf_plan(fr, nb, s_begin + b0, ws);
     const hipError_t e = dispatch_traversal<false>(fr, stack_needed, [&](auto stack, auto trav) {
       constexpr int S = decltype(stack)::value, T = decltype(trav)::value;
-      return wf_batch<S, T>(sc, fr, wbs, accum, nb, counters, stream, *ps, stats);
+      return wf_batch<S, T>(sc, fr, plan, accum, counters, stream, *ps, stats);
     });
     if (e != hipSuccess) return e;
   }
