@@ -93,6 +93,11 @@ static int fail(int code, const char* fmt, ...) {
   return code;
 }
 
+// The same slot for the entry points of other translation units (pt_denoise.hip).
+namespace ptmi {
+int set_last_error(int code, const char* msg) { return fail(code, "%s", msg); }
+}  // namespace ptmi
+
 static int check_hip(hipError_t e, const char* what) {
   if (e != hipSuccess) return fail(PTMI_EHIP, "%s: %s", what, hipGetErrorString(e));
   return PTMI_OK;

@@ -14,7 +14,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, post
 from .scene_data import DeviceLayout, SceneArrays, camera_upload, pack_device
 
 
@@ -151,6 +151,7 @@ class Integrator:
         self._reset_event = None  # counter reset the next overlapped trace must wait for
         self._ov = None  # side streams, workspaces and events of render_mk_overlapped, made by its first call
         self._n_active = torch.zeros(1, dtype=torch.int32, device=dscene.device)  # tile_update's readback slot
+        self._dn_ws = None  # denoise's two working images, made by its first call
 
     def _call(self, name, *args):
         """One C-ABI call by export name; a non-zero return raises PtmiError with ptmi_last_error()."""
@@ -421,6 +422,38 @@ class Integrator:
                 stream.synchronize()
             tiles['n'] = int(self._n_active.item())
         return tiles['n']
+
+    # ------------------------------------------------ post-processing (ptmi.post)
+    def denoise(self, accum, stats, iterations=5, sigma=4.0, out=None, var=None, stream=None):
+        """Variance-guided a-trous filter of accum by the error estimates in
+        stats (ptmi_denoise, include/ptmi_post.h), asynchronous on ``stream``.
+        Returns (rgb (H, W, 3) f32, var (H, W) f32: the variance the filter
+        claims for the result); ``out`` and ``var`` are used if given. The
+        workspace is cached on the integrator."""
+        lib = post.load()
+        dev = self.scene.device
+        if not (isinstance(accum, torch.Tensor) and accum.dtype == torch.float32 and accum.is_contiguous()
+                and accum.dim() == 3 and accum.shape[2] == 3 and accum.device == dev):
+            raise _lib.PtmiError(f'accum must be a contiguous float32 tensor of shape (H, W, 3) on {dev}')
+        h, w = int(accum.shape[0]), int(accum.shape[1])
+        _check_stats(stats, h, w, dev)
+        need = post.workspace_bytes(w, h)
+        with self._dev():
+            if out is None:
+                out = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
+            if var is None:
+                var = torch.empty((h, w), dtype=torch.float32, device=dev)
+            for t, shape, name in ((out, (h, w, 3), 'out'), (var, (h, w), 'var')):
+                if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.is_contiguous()
+                        and tuple(t.shape) == shape and t.device == dev):
+                    raise _lib.PtmiError(f'{name} must be a contiguous float32 tensor of shape {shape} on {dev}')
+            if self._dn_ws is None or self._dn_ws.numel() * 4 < need:
+                self._dn_ws = None
+                self._dn_ws = torch.empty(need // 4, dtype=torch.float32, device=dev)
+            _lib.check(lib.ptmi_denoise(accum.data_ptr(), stats.data_ptr(), w, h, int(iterations), float(sigma),
+                                        self._dn_ws.data_ptr(), self._dn_ws.numel() * 4, out.data_ptr(),
+                                        var.data_ptr(), self._stream(stream)), 'ptmi_denoise')
+        return out, var
 
     def _after_traces(self, stream):
         """Make `stream` wait for the overlapped traces in flight: they add to

@@ -29,9 +29,15 @@ and renders passes of the 64-pixel tiles whose error estimate is still above
 a target; ``noise_map()`` / ``sample_count_map()`` expose the estimates, the
 image divides each pixel by its own sample count, and checkpoints carry the
 extra state.
+
+Denoising (no counterpart in the reference): after a ``render_adaptive``,
+``denoise`` filters the accumulator by the per-pixel error estimates into
+``denoised``; ``image_u8(denoised=True)`` / ``write_denoised_image`` give the
+8-bit result. Derived data: not checkpointed.
 """
 from __future__ import annotations
 
+import os
 import time
 
 import numpy as np
@@ -73,6 +79,10 @@ class MI355XRenderer:
         self._tiles = None
         self._adaptive = None
         self.adaptive_passes = []
+        # denoise(): the filtered image, the variance it claims, the seconds it took (derived: not checkpointed)
+        self.denoised = None
+        self.denoised_var = None
+        self.denoise_seconds = None
         # launches per progress report: one launch renders many samples (path regeneration)
         self.samples_per_launch = int(samples_per_launch)
         device.require_gpu()
@@ -189,6 +199,7 @@ class MI355XRenderer:
         else:
             self.integrator.clear_stats(self.frame, self.stats)
         self._tiles = self.integrator.new_tiles(self.frame)
+        self.denoised = self.denoised_var = self.denoise_seconds = None  # of the render this one replaces
 
     def render_adaptive(self, target_error, pass_spp=None, min_spp=16, max_spp=None, integrator='megakernel',
                         resume=False, enable_preview: bool = True):
@@ -279,6 +290,24 @@ class MI355XRenderer:
         if self.stats is None:
             raise ValueError('no adaptive render yet')
         return self.stats[..., 0].cpu().numpy().astype(np.int32)
+
+    def denoise(self, iterations=5, sigma=4.0):
+        """Variance-guided a-trous filter of the accumulator by the per-pixel
+        error estimates of the stats render that filled it (Integrator.denoise,
+        include/ptmi_post.h). Stores ``denoised`` ((height, width, 3) f32
+        tensor, linear, already divided by the sample counts) and
+        ``denoised_var`` ((height, width): the variance of the mean luminance
+        the filter claims) and returns ``denoised``. A uniform render with
+        stats is render_adaptive(target_error=0, min_spp=N, max_spp=N). Single
+        device: a multi-GPU render gathers the accumulator only, not the stats."""
+        if not self._is_adaptive():
+            raise ValueError('no stats: render through render_adaptive')
+        import torch
+        t0 = time.time()
+        self.denoised, self.denoised_var = self.integrator.denoise(self.accum, self.stats, iterations, sigma)
+        torch.cuda.synchronize(self.integrator.scene.device)
+        self.denoise_seconds = time.time() - t0
+        return self.denoised
 
     def _is_adaptive(self):
         return self._integrator_label.startswith('adaptive-') and self.stats is not None
@@ -389,7 +418,11 @@ class MI355XRenderer:
             self._tiles = dict(self._resume_tiles, grid=(tx, ty))
 
     # ----------------------------------------------------------------- output
-    def image_u8(self, sample_count=None):
+    def image_u8(self, sample_count=None, denoised=False):
+        if denoised:  # denoise()'s result is already divided by the sample counts
+            if self.denoised is None:
+                raise ValueError('no denoised image: call denoise() first')
+            return self.integrator.tonemap(self.denoised, 1).cpu().numpy()
         if sample_count is None and self._is_adaptive():  # each pixel by its own sample count
             return self.integrator.tonemap(self.accum, stats=self.stats).cpu().numpy()
         spp = self.cam.samples_per_pixel if sample_count is None else sample_count
@@ -402,6 +435,17 @@ class MI355XRenderer:
         print(f'\nImage saved to {self.img_path}')
 
     _write_image = write_image
+
+    def write_denoised_image(self, path=None):
+        """PNG of the tone-mapped denoise() result, by default next to the
+        image as <name>_denoised.png."""
+        from PIL import Image
+        if path is None:
+            root, ext = os.path.splitext(self.img_path)
+            path = f'{root}_denoised{ext or ".png"}'
+        Image.fromarray(self.image_u8(denoised=True), mode='RGB').save(path)
+        print(f'\nDenoised image saved to {path}')
+        return path
 
     def _get_rr_stats(self):
         """Russian-roulette statistics of the last render (renderer.py:481-500)
@@ -475,6 +519,8 @@ class MI355XRenderer:
                 print(f'  pass {q["pass"] + 1:3d}: {q["active_tiles"]:7d} | {q["traced"]:13,} | '
                       f'{100.0 * q["traced"] / uniform:6.2f}%')
             print(f'  total: {total:,} of {uniform:,} samples ({100.0 * total / uniform:.1f}%)')
+        if self.denoise_seconds is not None:
+            print(f'Denoise Time: {1e3 * self.denoise_seconds:8.2f}ms')
 
     _print_stats = print_statistics
 
