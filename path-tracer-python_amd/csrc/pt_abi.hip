@@ -235,6 +235,15 @@ static int to_dev(const ptmi_scene_view* scene, const ptmi_frame* frame, DevScen
   return check_traversal(sc, fr);
 }
 
+// The same prologue for the guide trace of another translation unit (pt_guide.hip).
+namespace ptmi {
+int guide_to_dev(const ptmi_scene_view* scene, const ptmi_frame* frame, DevScene& sc, DevFrame& fr, int32_t& slots) {
+  if (int rc = to_dev(scene, frame, sc, fr)) return rc;
+  slots = stack_needed(scene);
+  return PTMI_OK;
+}
+}  // namespace ptmi
+
 static int check_accum(const float* accum) { return accum ? PTMI_OK : fail(PTMI_EINVAL, "accum is NULL"); }
 static int check_stats(const float* stats) {
   return bad16(stats) ? fail(PTMI_EINVAL, "stats NULL/misaligned") : PTMI_OK;

@@ -14,7 +14,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib, post
+from . import _lib, guide, post
 from .scene_data import DeviceLayout, SceneArrays, camera_upload, pack_device
 
 
@@ -424,6 +424,32 @@ class Integrator:
         return tiles['n']
 
     # ------------------------------------------------ post-processing (ptmi.post)
+    def _check_denoise_inputs(self, accum, stats):
+        dev = self.scene.device
+        if not (isinstance(accum, torch.Tensor) and accum.dtype == torch.float32 and accum.is_contiguous()
+                and accum.dim() == 3 and accum.shape[2] == 3 and accum.device == dev):
+            raise _lib.PtmiError(f'accum must be a contiguous float32 tensor of shape (H, W, 3) on {dev}')
+        h, w = int(accum.shape[0]), int(accum.shape[1])
+        _check_stats(stats, h, w, dev)
+        return h, w
+
+    def _denoise_buffers(self, h, w, out, var):
+        """The outputs (made if not given) and the cached workspace of a denoise call."""
+        dev = self.scene.device
+        need = post.workspace_bytes(w, h)
+        if out is None:
+            out = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
+        if var is None:
+            var = torch.empty((h, w), dtype=torch.float32, device=dev)
+        for t, shape, name in ((out, (h, w, 3), 'out'), (var, (h, w), 'var')):
+            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.is_contiguous()
+                    and tuple(t.shape) == shape and t.device == dev):
+                raise _lib.PtmiError(f'{name} must be a contiguous float32 tensor of shape {shape} on {dev}')
+        if self._dn_ws is None or self._dn_ws.numel() * 4 < need:
+            self._dn_ws = None
+            self._dn_ws = torch.empty(need // 4, dtype=torch.float32, device=dev)
+        return out, var, self._dn_ws
+
     def denoise(self, accum, stats, iterations=5, sigma=4.0, out=None, var=None, stream=None):
         """Variance-guided a-trous filter of accum by the error estimates in
         stats (ptmi_denoise, include/ptmi_post.h), asynchronous on ``stream``.
@@ -431,28 +457,48 @@ class Integrator:
         claims for the result); ``out`` and ``var`` are used if given. The
         workspace is cached on the integrator."""
         lib = post.load()
+        h, w = self._check_denoise_inputs(accum, stats)
+        with self._dev():
+            out, var, ws = self._denoise_buffers(h, w, out, var)
+            _lib.check(lib.ptmi_denoise(accum.data_ptr(), stats.data_ptr(), w, h, int(iterations), float(sigma),
+                                        ws.data_ptr(), ws.numel() * 4, out.data_ptr(),
+                                        var.data_ptr(), self._stream(stream)), 'ptmi_denoise')
+        return out, var
+
+    # ------------------------------------------------ guides (ptmi.guide)
+    def trace_guides(self, frame, out=None, stream=None):
+        """First-hit guide buffers of a whole, unbanded frame (ptmi_guide_trace,
+        include/ptmi_guide.h): an (H, W, 8) f32 tensor {nx, ny, nz, depth, ar,
+        ag, ab, hit} from one deterministic primary ray per pixel,
+        asynchronous on ``stream``; ``out`` is used if given."""
+        lib = guide.load()
         dev = self.scene.device
-        if not (isinstance(accum, torch.Tensor) and accum.dtype == torch.float32 and accum.is_contiguous()
-                and accum.dim() == 3 and accum.shape[2] == 3 and accum.device == dev):
-            raise _lib.PtmiError(f'accum must be a contiguous float32 tensor of shape (H, W, 3) on {dev}')
-        h, w = int(accum.shape[0]), int(accum.shape[1])
-        _check_stats(stats, h, w, dev)
-        need = post.workspace_bytes(w, h)
+        shape = (int(frame.height), int(frame.width), guide.GUIDE_CHANNELS)
         with self._dev():
             if out is None:
-                out = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
-            if var is None:
-                var = torch.empty((h, w), dtype=torch.float32, device=dev)
-            for t, shape, name in ((out, (h, w, 3), 'out'), (var, (h, w), 'var')):
-                if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.is_contiguous()
-                        and tuple(t.shape) == shape and t.device == dev):
-                    raise _lib.PtmiError(f'{name} must be a contiguous float32 tensor of shape {shape} on {dev}')
-            if self._dn_ws is None or self._dn_ws.numel() * 4 < need:
-                self._dn_ws = None
-                self._dn_ws = torch.empty(need // 4, dtype=torch.float32, device=dev)
-            _lib.check(lib.ptmi_denoise(accum.data_ptr(), stats.data_ptr(), w, h, int(iterations), float(sigma),
-                                        self._dn_ws.data_ptr(), self._dn_ws.numel() * 4, out.data_ptr(),
-                                        var.data_ptr(), self._stream(stream)), 'ptmi_denoise')
+                out = torch.empty(shape, dtype=torch.float32, device=dev)
+            _check_guides(out, shape[0], shape[1], dev)
+            _lib.check(lib.ptmi_guide_trace(self.scene.view, frame, out.data_ptr(), self._stream(stream)),
+                       'ptmi_guide_trace')
+        return out
+
+    def denoise_guided(self, accum, stats, guides, iterations=5, sigma=4.0, sigma_z=0.1, sigma_a=0.2,
+                       normal_power_log2=5, demodulate=True, out=None, var=None, stream=None):
+        """``denoise`` with the guides of ``trace_guides`` as further
+        edge-stopping terms (relative depth, albedo, normal) and, with
+        ``demodulate``, the filter run on colour divided by the albedo
+        (ptmi_denoise_guided, include/ptmi_guide.h). Same return values and
+        the same cached workspace as ``denoise``."""
+        lib = guide.load()
+        dev = self.scene.device
+        h, w = self._check_denoise_inputs(accum, stats)
+        _check_guides(guides, h, w, dev)
+        prm = guide.params(iterations, sigma, sigma_z, sigma_a, normal_power_log2, demodulate)
+        with self._dev():
+            out, var, ws = self._denoise_buffers(h, w, out, var)
+            _lib.check(lib.ptmi_denoise_guided(accum.data_ptr(), stats.data_ptr(), guides.data_ptr(), w, h,
+                                               C.byref(prm), ws.data_ptr(), ws.numel() * 4, out.data_ptr(),
+                                               var.data_ptr(), self._stream(stream)), 'ptmi_denoise_guided')
         return out, var
 
     def _after_traces(self, stream):
@@ -503,6 +549,15 @@ def _check_stats(stats, height, width, device=None):
         raise _lib.PtmiError(f'stats must be a contiguous cuda float32 tensor of shape ({height}, {width}, 4)')
     if device is not None and stats.device != device:
         raise _lib.PtmiError(f'stats is on {stats.device}, the scene on {device}')
+
+
+def _check_guides(guides, height, width, device=None):
+    shape = (height, width, guide.GUIDE_CHANNELS)
+    if not (isinstance(guides, torch.Tensor) and guides.is_cuda and guides.dtype == torch.float32
+            and guides.is_contiguous() and tuple(guides.shape) == shape):
+        raise _lib.PtmiError(f'guides must be a contiguous cuda float32 tensor of shape {shape}')
+    if device is not None and guides.device != device:
+        raise _lib.PtmiError(f'guides is on {guides.device}, the scene on {device}')
 
 
 def _check_accum(accum, frame, device=None):

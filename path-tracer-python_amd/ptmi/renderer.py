@@ -33,7 +33,10 @@ extra state.
 Denoising (no counterpart in the reference): after a ``render_adaptive``,
 ``denoise`` filters the accumulator by the per-pixel error estimates into
 ``denoised``; ``image_u8(denoised=True)`` / ``write_denoised_image`` give the
-8-bit result. Derived data: not checkpointed.
+8-bit result. ``denoise(guided=True)`` adds first-hit normal,
+depth and albedo guides as edge-stopping terms; ``guides()`` / ``guide_maps()``
+give them as a tensor or as numpy AOVs. Derived data: not
+checkpointed.
 """
 from __future__ import annotations
 
@@ -83,6 +86,10 @@ class MI355XRenderer:
         self.denoised = None
         self.denoised_var = None
         self.denoise_seconds = None
+        # guides(): the guide image of the camera it was traced for, and the seconds the trace took
+        self._guides = None
+        self._guides_key = None
+        self.guide_trace_seconds = None
         # launches per progress report: one launch renders many samples (path regeneration)
         self.samples_per_launch = int(samples_per_launch)
         device.require_gpu()
@@ -291,7 +298,35 @@ class MI355XRenderer:
             raise ValueError('no adaptive render yet')
         return self.stats[..., 0].cpu().numpy().astype(np.int32)
 
-    def denoise(self, iterations=5, sigma=4.0):
+    def _guide_key(self):
+        f = self.frame
+        cam = tuple(float(v) for k in ('center', 'pixel00', 'delta_u', 'delta_v') for v in getattr(f.cam, k))
+        return cam + (int(f.width), int(f.height), int(f.traversal))
+
+    def guides(self):
+        """First-hit guide buffers of the current camera (Integrator.trace_guides,
+        include/ptmi_guide.h): a (height, width, 8) f32 tensor {nx, ny, nz,
+        depth, ar, ag, ab, hit}. Traced once per camera and scene and cached;
+        one deterministic primary ray per pixel, independent of the samples
+        rendered."""
+        key = self._guide_key()
+        if self._guides is None or self._guides_key != key:
+            import torch
+            t0 = time.time()
+            self._guides = self.integrator.trace_guides(self.frame)
+            torch.cuda.synchronize(self.integrator.scene.device)
+            self.guide_trace_seconds = time.time() - t0
+            self._guides_key = key
+        return self._guides
+
+    def guide_maps(self):
+        """The guides as numpy AOVs: {'normal': (H, W, 3), 'depth': (H, W),
+        'albedo': (H, W, 3), 'hit': (H, W) bool}; depth is 1e10 where hit is False."""
+        g = self.guides().cpu().numpy()
+        return {'normal': g[..., 0:3].copy(), 'depth': g[..., 3].copy(), 'albedo': g[..., 4:7].copy(),
+                'hit': g[..., 7] != 0}
+
+    def denoise(self, iterations=5, sigma=4.0, guided=False, **guided_params):
         """Variance-guided a-trous filter of the accumulator by the per-pixel
         error estimates of the stats render that filled it (Integrator.denoise,
         include/ptmi_post.h). Stores ``denoised`` ((height, width, 3) f32
@@ -299,12 +334,24 @@ class MI355XRenderer:
         ``denoised_var`` ((height, width): the variance of the mean luminance
         the filter claims) and returns ``denoised``. A uniform render with
         stats is render_adaptive(target_error=0, min_spp=N, max_spp=N). Single
-        device: a multi-GPU render gathers the accumulator only, not the stats."""
+        device: a multi-GPU render gathers the accumulator only, not the stats.
+
+        guided=True: the same with the guides of ``guides()`` as further
+        edge-stopping terms (Integrator.denoise_guided, include/ptmi_guide.h);
+        ``guided_params`` are its sigma_z, sigma_a, normal_power_log2 and
+        demodulate."""
         if not self._is_adaptive():
             raise ValueError('no stats: render through render_adaptive')
+        if guided_params and not guided:
+            raise ValueError(f'{sorted(guided_params)} need guided=True')
         import torch
+        guides = self.guides() if guided else None  # (its own time is guide_trace_seconds)
         t0 = time.time()
-        self.denoised, self.denoised_var = self.integrator.denoise(self.accum, self.stats, iterations, sigma)
+        if guided:
+            self.denoised, self.denoised_var = self.integrator.denoise_guided(self.accum, self.stats, guides,
+                                                                              iterations, sigma, **guided_params)
+        else:
+            self.denoised, self.denoised_var = self.integrator.denoise(self.accum, self.stats, iterations, sigma)
         torch.cuda.synchronize(self.integrator.scene.device)
         self.denoise_seconds = time.time() - t0
         return self.denoised
@@ -521,6 +568,8 @@ class MI355XRenderer:
             print(f'  total: {total:,} of {uniform:,} samples ({100.0 * total / uniform:.1f}%)')
         if self.denoise_seconds is not None:
             print(f'Denoise Time: {1e3 * self.denoise_seconds:8.2f}ms')
+        if self.guide_trace_seconds is not None:
+            print(f'Guide Trace Time: {1e3 * self.guide_trace_seconds:8.2f}ms')
 
     _print_stats = print_statistics
 
