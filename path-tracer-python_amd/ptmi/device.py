@@ -14,7 +14,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib, guide, post
+from . import _lib, guide, post, temporal
 from .scene_data import DeviceLayout, SceneArrays, camera_upload, pack_device
 
 
@@ -500,6 +500,38 @@ class Integrator:
                                                C.byref(prm), ws.data_ptr(), ws.numel() * 4, out.data_ptr(),
                                                var.data_ptr(), self._stream(stream)), 'ptmi_denoise_guided')
         return out, var
+
+    # ------------------------------------------------ temporal reprojection (ptmi.temporal)
+    def reproject(self, cur_cam, prev_cam, guides_cur, guides_prev, accum, stats, *, max_history=32.0, sigma_z=0.1,
+                  normal_min=0.9, sigma_a=0.2, out=None, stream=None):
+        """The history ``accum``, ``stats`` of a stats render from ``prev_cam``
+        carried to ``cur_cam`` (ptmi_reproject, include/ptmi_temporal.h): every
+        pixel of the current frame finds its surface point in the previous
+        frame, checks by both guide images (``trace_guides`` of each camera)
+        that it is the same surface, and takes colour, per-sample luminance
+        variance and a sample count capped at ``max_history`` from there;
+        pixels without history are zero. The cameras are camera-upload dicts
+        or ``_lib.Camera`` values. Returns (accum, stats) as new tensors, or
+        the pair ``out`` if given; asynchronous on ``stream``."""
+        lib = temporal.load()
+        dev = self.scene.device
+        h, w = self._check_denoise_inputs(accum, stats)
+        _check_guides(guides_cur, h, w, dev)
+        _check_guides(guides_prev, h, w, dev)
+        cur, prev = temporal.camera(cur_cam), temporal.camera(prev_cam)
+        prm = temporal.params(max_history, sigma_z, normal_min, sigma_a)
+        with self._dev():
+            if out is None:
+                out = (torch.empty_like(accum), torch.empty_like(stats))
+            out_accum, out_stats = out
+            self._check_denoise_inputs(out_accum, out_stats)
+            if tuple(out_accum.shape) != tuple(accum.shape):
+                raise _lib.PtmiError(f'out must be an (accum, stats) pair of a {w} x {h} image')
+            _lib.check(lib.ptmi_reproject(C.byref(cur), C.byref(prev), guides_cur.data_ptr(), guides_prev.data_ptr(),
+                                          accum.data_ptr(), stats.data_ptr(), w, h, C.byref(prm),
+                                          out_accum.data_ptr(), out_stats.data_ptr(), self._stream(stream)),
+                       'ptmi_reproject')
+        return out_accum, out_stats
 
     def _after_traces(self, stream):
         """Make `stream` wait for the overlapped traces in flight: they add to

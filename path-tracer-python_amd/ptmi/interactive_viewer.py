@@ -15,6 +15,11 @@ Progressive sampling launches ``display_interval`` samples per call (the
 reference launches one per call, :389): sample i of a pixel is keyed by
 (seed, pixel, i), so the accumulated image is bit-identical however the
 samples are batched.
+
+``InteractiveViewer(..., temporal=True, max_history=32)`` (no counterpart in
+the reference): a camera move reprojects the accumulated history to the new
+camera instead of clearing it. The default, temporal=False, is
+the behaviour above, bit for bit.
 """
 from __future__ import annotations
 
@@ -50,8 +55,18 @@ def orbit_step(theta, phi, delta_x, delta_y, velocity=(0.3, 0.3)):
 
 
 class InteractiveViewer(MI355XRenderer):
-    def __init__(self, world, cam, img_path: str, **kwargs):
+    def __init__(self, world, cam, img_path: str, temporal: bool = False, max_history: float = 32, **kwargs):
         super().__init__(world, cam, img_path, **kwargs)
+        # temporal=True: a camera move reprojects the accumulated history to the
+        # new camera instead of clearing it (MI355XRenderer.reproject_history,
+        # DESIGN.md §15). The samples then always go through the stats path.
+        self.temporal = bool(temporal)
+        self.max_history = float(max_history)
+        self.history_fraction = None  # pixels with history after the last reprojection
+        self._sample_origin = 0  # RNG sample index of current_sample == 0: rises across restarts
+        self._history_cam = None  # camera and guides of the last render: what the rendered history was seen with
+        self._history_guides = None
+        self._history_kept = False  # the last restart reprojected: the next render keeps accum / stats
         self.mouse_down = False
         self.last_mouse_x = 0
         self.last_mouse_y = 0
@@ -82,7 +97,39 @@ class InteractiveViewer(MI355XRenderer):
         self.cam.initialize()
         self._upload_camera_to_gpu()
 
+    @property
+    def next_sample_index(self):
+        """RNG sample index of the next sample rendered: current_sample, plus,
+        in a temporal viewer, the samples rendered before the restarts."""
+        return self._sample_origin + self.current_sample
+
+    def _restart_with_history(self):
+        """The temporal restart: the rendered history reprojected to the
+        camera uploaded since. _history_cam / _history_guides stay those of the
+        last camera samples were rendered at, so a further restart with no
+        sample in between (the next step of one drag) reprojects that same
+        rendered history again (reproject_history(again=True)) instead of
+        resampling the reprojected one. current_sample restarts at 0 as the
+        progress count; the sample index goes on from _sample_origin, so no
+        pixel draws the streams of its history again."""
+        again = self._history_kept and self.current_sample == 0
+        self._sample_origin += self.current_sample
+        self.current_sample = 0
+        self.sample_times = []
+        self.render_start_time = time.time()
+        self.history_fraction = self.reproject_history(self._history_cam, self._history_guides, again=again,
+                                                       max_history=self.max_history)
+        self._history_kept = True
+        self.integrator.reset_counters()
+        self.is_rendering_active = True
+        print(f"\n{'─' * 60}\nCamera rotated - history reprojected to {100.0 * self.history_fraction:.1f}% of the "
+              f"pixels (at most {self.max_history:g} samples each)\n{'─' * 60}")
+
     def restart_rendering(self):
+        if self.temporal and self.stats is not None and self._history_guides is not None and \
+                (self.current_sample > 0 or self._history_kept):
+            return self._restart_with_history()
+        self._history_kept = False
         self.current_sample = 0
         self.sample_times = []
         self.render_start_time = time.time()
@@ -131,7 +178,13 @@ class InteractiveViewer(MI355XRenderer):
         MI355XRenderer.render_adaptive) and the render stops early once every
         tile has min_spp samples and an error of at most target_error; the
         image then divides by the samples rendered. target_error=None is the
-        reference's behaviour."""
+        reference's behaviour.
+
+        In a ``temporal=True`` viewer the samples go through the stats path
+        with or without ``target_error``, the guides of the camera are traced
+        once, and a call that follows a reprojecting restart keeps the
+        history: sample index ``next_sample_index`` goes on where the last
+        render stopped, and the image divides each pixel by its own count."""
         import torch
         spp = int(self.cam.samples_per_pixel)
         print('\nInteractiveViewer')
@@ -139,13 +192,24 @@ class InteractiveViewer(MI355XRenderer):
         print(f'Spheres: {self.num_spheres} | BVH Nodes: {self.num_bvh_nodes}')
         self._upload_camera_to_gpu()
         t0 = time.time()
-        self.render_sample(0)  # warm-up sample, cleared (interactive_viewer.py:355-359)
-        torch.cuda.synchronize(self.dscene.device)
-        self.clear_accumulation_buffer()
-        if target_error is not None:
+        stats_path = target_error is not None or self.temporal
+        if self.temporal and self._history_kept:
+            # after a reprojecting restart: accum / stats hold the history, so the
+            # warm-up sample goes to a scratch accumulator and nothing is cleared
+            self.integrator.render_mk(self.frame, torch.empty_like(self.accum), 0, 1)
+            torch.cuda.synchronize(self.dscene.device)
             self._integrator_label = 'adaptive-megakernel'
-            self._adaptive = None  # no pass schedule: not resumable as a render_adaptive() run
-            self._adaptive_reset()
+        else:
+            self.render_sample(0)  # warm-up sample, cleared (interactive_viewer.py:355-359)
+            torch.cuda.synchronize(self.dscene.device)
+            self.clear_accumulation_buffer()
+            if stats_path:
+                self._integrator_label = 'adaptive-megakernel'
+                self._adaptive = None  # no pass schedule: not resumable as a render_adaptive() run
+                self._adaptive_reset()
+        if self.temporal:  # the guides of this camera, traced once: what a later restart reprojects by
+            self._history_cam, self._history_guides = self.frame.cam, self.guides()
+            self._history_kept = False
         self.integrator.reset_counters()
         print(f'  Kernel Warmup: {(time.time() - t0) * 1000:6.2f}ms')
         self.setup_interactive_preview()
@@ -158,11 +222,13 @@ class InteractiveViewer(MI355XRenderer):
             if self.current_sample == 0:
                 n = 1  # the reference prints sample 1
             t = time.time()
-            if target_error is None:
+            if not stats_path:
                 self.integrator.render_mk(self.frame, self.accum, self.current_sample, n)
             else:
-                self.integrator.render_mk_stats(self.frame, self.accum, self.stats, self.current_sample, n)
-                left = self.integrator.tile_update(self.frame, self.stats, target_error, min_spp, spp, self._tiles)
+                self.integrator.render_mk_stats(self.frame, self.accum, self.stats, self.next_sample_index, n)
+                if target_error is not None:
+                    left = self.integrator.tile_update(self.frame, self.stats, target_error, min_spp, spp,
+                                                       self._tiles)
             torch.cuda.synchronize(self.dscene.device)
             dt = (time.time() - t) / n
             self.sample_times += [dt] * n

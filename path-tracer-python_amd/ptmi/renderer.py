@@ -37,6 +37,12 @@ Denoising (no counterpart in the reference): after a ``render_adaptive``,
 depth and albedo guides as edge-stopping terms; ``guides()`` / ``guide_maps()``
 give them as a tensor or as numpy AOVs. Derived data: not
 checkpointed.
+
+Temporal reprojection (no counterpart in the reference):
+``reproject_history(prev_camera, prev_guides)`` carries the accumulator and
+the stats of a stats render to the camera uploaded since, by the guides of both
+cameras; InteractiveViewer(temporal=True) does so on every
+camera move. Derived state: not checkpointed.
 """
 from __future__ import annotations
 
@@ -90,6 +96,8 @@ class MI355XRenderer:
         self._guides = None
         self._guides_key = None
         self.guide_trace_seconds = None
+        # reproject_history(): the (accum, stats) pair it writes into next, swapped with the live pair on each call
+        self._history_spare = None
         # launches per progress report: one launch renders many samples (path regeneration)
         self.samples_per_launch = int(samples_per_launch)
         device.require_gpu()
@@ -325,6 +333,46 @@ class MI355XRenderer:
         g = self.guides().cpu().numpy()
         return {'normal': g[..., 0:3].copy(), 'depth': g[..., 3].copy(), 'albedo': g[..., 4:7].copy(),
                 'hit': g[..., 7] != 0}
+
+    def reproject_history(self, prev_camera, prev_guides, again=False, **params):
+        """Carry ``accum`` and ``stats`` of a stats render from ``prev_camera``
+        (its camera-upload dict or ptmi_camera) with the guides ``prev_guides``
+        it had to the current camera (Integrator.reproject,
+        include/ptmi_temporal.h; ``params`` are its max_history, sigma_z,
+        normal_min and sigma_a). The guides of the current camera are traced
+        or taken from the cache (``prev_guides`` may be that same tensor: the
+        camera has not moved); the result is written into spare tensors that
+        are then swapped in, the tile states start over and ``denoised`` is
+        dropped. Returns the fraction of pixels with history.
+
+        ``again=True``, for a camera that moved on with no sample rendered
+        since the last call: the history that call reprojected (kept as the
+        spare pair; ``prev_camera`` and ``prev_guides`` are still its own) is
+        reprojected to the current camera and replaces that call's result, so
+        a drag of many steps resamples and caps the rendered history once, not
+        once per step. Derived state: not checkpointed."""
+        if self.stats is None:
+            raise ValueError('no stats: render through the stats path (render_adaptive) first')
+        import torch
+        guides = self.guides()
+        spare = self._history_spare
+        if spare is not None and tuple(spare[0].shape) != tuple(self.accum.shape):
+            spare = None
+        if again:
+            if spare is None:
+                raise ValueError('again=True needs an earlier reproject_history() of this image size')
+            self.integrator.reproject(self.frame.cam, prev_camera, guides, prev_guides, spare[0], spare[1],
+                                      out=(self.accum, self.stats), **params)
+        else:
+            if spare is None:
+                spare = (torch.empty_like(self.accum), torch.empty_like(self.stats))
+            out = self.integrator.reproject(self.frame.cam, prev_camera, guides, prev_guides, self.accum, self.stats,
+                                            out=spare, **params)
+            self._history_spare = (self.accum, self.stats)
+            self.accum, self.stats = out
+        self._tiles = self.integrator.new_tiles(self.frame)
+        self.denoised = self.denoised_var = self.denoise_seconds = None
+        return int((self.stats[..., 0] > 0).sum().item()) / (self.stats.shape[0] * self.stats.shape[1])
 
     def denoise(self, iterations=5, sigma=4.0, guided=False, **guided_params):
         """Variance-guided a-trous filter of the accumulator by the per-pixel
