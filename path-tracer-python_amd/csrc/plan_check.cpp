@@ -8,7 +8,9 @@
 // wavefront workspace's regions are aligned, disjoint and inside the
 // workspace; the work-item counts respect the id limits; the megakernel's
 // unit decode covers every (tile, sample, lane) exactly once and the
-// wavefront's item decode every (sample, pixel). Three plans are
+// wavefront's item decode every (sample, pixel); a tile-listed wavefront
+// plan's regions lie inside the unlisted workspace and its decode reaches
+// every (listed tile, sample, lane) once and nothing else. Three plans are
 // pinned literally: the fields that set speed and that no image test sees.
 #include <stdint.h>
 #include <stdio.h>
@@ -228,10 +230,72 @@ static void check_wf_cover(const DevFrame& fr, const WfBufs& wb) {
   CHECK(std::all_of(seen.begin(), seen.end(), [](uint8_t c) { return c == 1; }));
 }
 
-static void check_wf(const DevFrame& fr, int32_t nb) {
+// COPY of the LISTED decode_item (pt_wavefront.hip; WfList<true> holds the
+// list, the grid's tile count and tw_log2), restated on the host.
+static int64_t wf_listed_slot_host(const DevFrame& fr, const WfBufs& wb, const std::vector<int32_t>& list,
+                                   const TileGrid& g, uint32_t k) {
+  const uint32_t per = 64u * (uint32_t)wb.csamp;
+  const uint32_t c = fdiv_host(k, wb.by_per), j = k - c * per;
+  const uint32_t blk = fdiv_host(c, wb.by_nsq), v = c - blk * (uint32_t)wb.nsq;
+  if (v >= list.size()) return -2;  // (never: the device would read past the list)
+  const int32_t id = list[v];
+  const bool in_grid = (uint32_t)id < (uint32_t)g.ntiles;
+  const uint32_t t = in_grid ? (uint32_t)id : 0u;
+  const int32_t ty = (int32_t)fdiv_host(t, wb.by_sqx), tx = (int32_t)t - ty * wb.sq_x;
+  const uint32_t lane = j & 63u;
+  const int32_t lx = (tx << g.tw_log2) + (int32_t)(lane & ((1u << g.tw_log2) - 1u));
+  const int32_t lr = ty * (64 >> g.tw_log2) + (int32_t)(lane >> g.tw_log2);
+  const int32_t srel = (int32_t)blk * wb.csamp + (int32_t)(j >> 6);
+  if (!(in_grid && lx < fr.w && lr < fr.n_rows && srel < wb.batch)) return -1;
+  return (int64_t)srel * wb.npix + (lr * fr.w + lx);
+}
+
+// The listed decode reaches every (listed tile, sample, lane) inside the frame
+// exactly once (the ids are distinct) and no other staging slot. Batches of
+// more than 2^23 items, or whose staging has more than 2^26 slots, are
+// checked at every 4099th item against plain division.
+static void check_wf_listed_cover(const DevFrame& fr, const WfBufs& wb, const std::vector<int32_t>& list) {
+  const TileGrid g = tile_grid(fr);
+  const int32_t tw = 1 << g.tw_log2, th = 64 >> g.tw_log2;
+  auto plain = [&](uint32_t k) -> int64_t {
+    const uint32_t per = 64u * (uint32_t)wb.csamp, c = k / per, j = k % per;
+    const int32_t id = list[c % (uint32_t)list.size()];
+    const int32_t srel = (int32_t)(c / (uint32_t)list.size()) * wb.csamp + (int32_t)(j / 64u);
+    if (id < 0 || id >= g.ntiles) return -1;
+    const int32_t lx = (id % g.tiles_x) * tw + (int32_t)(j % 64u) % tw, lr = (id / g.tiles_x) * th + (int32_t)(j % 64u) / tw;
+    return lx < fr.w && lr < fr.n_rows && srel < wb.batch ? (int64_t)srel * wb.npix + ((int64_t)lr * fr.w + lx) : -1;
+  };
+  if (wb.nitems > (1 << 23) || (int64_t)wb.npix * wb.batch > (1ll << 26)) {
+    for (uint32_t k = 0; k < (uint32_t)wb.nitems; k += 4099) CHECK(wf_listed_slot_host(fr, wb, list, g, k) == plain(k));
+    for (int64_t k = (int64_t)wb.nitems - 64; k < wb.nitems; ++k)
+      if (k >= 0) CHECK(wf_listed_slot_host(fr, wb, list, g, (uint32_t)k) == plain((uint32_t)k));
+    return;
+  }
+  std::vector<uint8_t> seen((size_t)wb.npix * wb.batch, 0), want(seen.size(), 0);
+  for (uint32_t k = 0; k < (uint32_t)wb.nitems; ++k) {
+    const int64_t slot = wf_listed_slot_host(fr, wb, list, g, k);
+    CHECK(slot >= -1 && slot < (int64_t)seen.size());
+    if (slot >= 0 && slot < (int64_t)seen.size()) ++seen[(size_t)slot];
+  }
+  for (int32_t id : list) {
+    if (id < 0 || id >= g.ntiles) continue;
+    for (int32_t p = 0; p < 64; ++p) {
+      const int32_t lx = (id % g.tiles_x) * tw + p % tw, lr = (id / g.tiles_x) * th + p / tw;
+      if (lx < fr.w && lr < fr.n_rows)
+        for (int32_t s = 0; s < wb.batch; ++s) ++want[(size_t)s * wb.npix + ((size_t)lr * fr.w + lx)];
+    }
+  }
+  CHECK(seen == want);
+}
+
+// list != nullptr: the tile-listed plan of the same frame and batch.
+static void check_wf(const DevFrame& fr, int32_t nb, const std::vector<int32_t>* list = nullptr) {
   const int32_t npix = fr.w * fr.n_rows;
-  const WfPlan P = wf_plan(fr, nb, 7, kBase);
-  CHECK(P.total == wf_workspace_bytes(fr, nb));
+  const int32_t n_list = list ? (int32_t)list->size() : 0;
+  const WfPlan P = wf_plan(fr, nb, 7, kBase, list ? list->data() : nullptr, n_list);
+  // a listed plan lies inside the unlisted workspace, whose size does not change
+  if (list) CHECK(P.total <= wf_workspace_bytes(fr, nb));
+  else CHECK(P.total == wf_workspace_bytes(fr, nb));
   const uintptr_t base = (uintptr_t)kBase, end = base + P.total;
   const WfBufs& w0 = P.wb[0];
   std::vector<Region> R;
@@ -275,7 +339,14 @@ static void check_wf(const DevFrame& fr, int32_t nb) {
   // the memset before a batch zeroes the pool counters and every pipe's lines
   CHECK((uintptr_t)w0.next + kCtlWords * sizeof(int32_t) == end);
 
-  CHECK(w0.sq_x == (fr.w + 7) / 8 && w0.nsq == w0.sq_x * ((fr.n_rows + 7) / 8));
+  if (list) {
+    CHECK(w0.sq_x == tile_grid(fr).tiles_x && w0.nsq == n_list);
+    // no more rays in flight than the listed paths, nor than the unlisted batch's
+    CHECK(w0.capacity <= wf_plan(fr, nb, 7, kBase).wb[0].capacity);
+    CHECK((int64_t)nb <= wf_max_batch_listed(n_list));
+  } else {
+    CHECK(w0.sq_x == (fr.w + 7) / 8 && w0.nsq == w0.sq_x * ((fr.n_rows + 7) / 8));
+  }
   CHECK(w0.csamp >= 1 && w0.csamp <= PTMI_WF_CHUNK_SAMPLES && w0.csamp <= nb);
   CHECK(w0.nitems > 0 && w0.nitems % (64 * w0.csamp) == 0);
   CHECK((int64_t)w0.nitems >= 64ll * w0.nsq * nb);  // every (square, sample, lane) has an id
@@ -293,7 +364,8 @@ static void check_wf(const DevFrame& fr, int32_t nb) {
   CHECK((int64_t)P.grid * kWfBlock <= w0.capacity);
   CHECK((int64_t)P.grid_drain * kWfBlock >= work);
   CHECK(P.max_iters == (int64_t)w0.nitems * fr.max_depth + 2);
-  check_wf_cover(fr, w0);
+  if (list) check_wf_listed_cover(fr, w0, *list);
+  else check_wf_cover(fr, w0);
 }
 
 // ------------------------------------------------------------------ literal plans
@@ -368,6 +440,33 @@ int main() {
     for (int32_t nb : {1, 3, 16}) {
       snprintf(g_ctx, sizeof g_ctx, "%s: megakernel, %zu listed tiles, batch %d", c.name, list.size(), nb);
       check_mk(fr, nb, &list);
+      ++plans;
+    }
+  }
+  // tile-listed wavefront plans: n_list in {1, 5, 8, 9, ntiles} tiles spread
+  // over the grid, the last tile (an edge tile) among them and, from 5 ids on,
+  // one id outside the grid; then the listed id limit
+  for (const Case& c : frames()) {
+    const DevFrame& fr = c.fr;
+    const int32_t ntiles = tile_grid(fr).ntiles;
+    int32_t last = 0;
+    for (int32_t want : {1, 5, 8, 9, ntiles}) {
+      const int32_t n_list = std::min(want, ntiles);
+      if (n_list == last) continue;
+      last = n_list;
+      std::vector<int32_t> list(n_list);
+      for (int32_t k = 0; k < n_list; ++k) list[k] = (int32_t)((int64_t)k * ntiles / n_list);
+      list[n_list - 1] = ntiles - 1;
+      if (n_list >= 5 && n_list < ntiles) list[2] = ntiles;
+      for (int32_t nb : {1, 3, 5, 16}) {
+        snprintf(g_ctx, sizeof g_ctx, "%s: wavefront, %d listed tiles, batch %d", c.name, n_list, nb);
+        check_wf(fr, nb, &list);
+        ++plans;
+      }
+      const int64_t lmax = wf_max_batch_listed(n_list);
+      snprintf(g_ctx, sizeof g_ctx, "%s: wavefront, %d listed tiles, id limit %lld", c.name, n_list, (long long)lmax);
+      CHECK(lmax >= 1);
+      check_wf(fr, (int32_t)lmax, &list);  // (checks nitems + 2^24 <= 2^31)
       ++plans;
     }
   }

@@ -16,6 +16,7 @@
 #include <cstring>
 #include <string>
 
+#include "../../include/ptmi_wf_tiles.h"
 #include "pt_launch.hpp"
 #include "pt_prof.hpp"
 
@@ -268,28 +269,35 @@ static dim3 capped_grid(int64_t n) {
 // ------------------------------- one body per group of entry points (`what` names the public one)
 // Each keeps one order: scene, frame, traversal, the call's own arguments as
 // declared, then the no-op returns around the workspace check.
-enum RenderKind { kMkStaged, kWf, kWfStats };  // ptmi_mk_render_ws, ptmi_wf_render, ptmi_wf_render_stats
+// ptmi_mk_render_ws, ptmi_wf_render, ptmi_wf_render_stats, ptmi_wf_render_tiles_stats (the call has a tile list)
+enum RenderKind { kMkStaged, kWf, kWfStats, kWfTilesStats };
 
 static int render_ws_any(const char* what, RenderKind kind, const ptmi_scene_view* scene, const ptmi_frame* frame,
                          void* ws, size_t ws_bytes, float* accum, float* stats, int32_t s_begin, int32_t s_count,
-                         uint64_t* counters, void* stream) {
+                         uint64_t* counters, void* stream, const int32_t* tile_list = nullptr, int32_t n_tiles = 0) {
   DevScene sc;
   DevFrame fr;
   if (int rc = to_dev(scene, frame, sc, fr)) return rc;
   if (int rc = check_accum(accum)) return rc;
-  if (kind == kWfStats)
+  const bool listed = kind == kWfTilesStats;
+  if (kind == kWfStats || listed)
     if (int rc = check_stats(stats)) return rc;
+  if (listed && bad_tile_count(n_tiles, fr))
+    return fail(PTMI_EINVAL, "n_tiles %d outside [0, %lld]", n_tiles, (long long)tile_grid(fr).ntiles);
+  if (listed && n_tiles > 0 && (!tile_list || !aligned4(tile_list)))
+    return fail(PTMI_EINVAL, "tile_list NULL/misaligned");
   if (s_begin < 0 || s_count < 0) return fail(PTMI_EINVAL, "bad sample range");
   const int32_t npix = fr.w * fr.n_rows;
   if (npix == 0) return PTMI_OK;
   const size_t need = kind == kMkStaged ? mk_workspace_bytes(npix, 1) : wf_workspace_bytes(fr, 1);
   if (int rc = check_workspace(ws, ws_bytes, need, false)) return rc;
-  if (s_count == 0) return PTMI_OK;
+  if (s_count == 0 || (listed && n_tiles == 0)) return PTMI_OK;
   unsigned long long* cnt = (unsigned long long*)counters;
   const hipStream_t st = (hipStream_t)stream;
   const int32_t slots = stack_needed(scene);
   return check_hip(kind == kMkStaged ? mk_render_staged(sc, fr, slots, ws, ws_bytes, accum, s_begin, s_count, cnt, st)
-                                     : wf_render(sc, fr, slots, ws, ws_bytes, accum, s_begin, s_count, cnt, st, stats),
+                                     : wf_render(sc, fr, slots, ws, ws_bytes, accum, s_begin, s_count, cnt, st, stats,
+                                                 listed ? tile_list : nullptr, listed ? n_tiles : 0),
                    what);
 }
 
@@ -501,6 +509,15 @@ int ptmi_wf_render_stats(const ptmi_scene_view* scene, const ptmi_frame* frame, 
                          int32_t sample_count, uint64_t* counters, void* stream) {
   return render_ws_any("wf_render_stats", kWfStats, scene, frame, workspace, workspace_bytes, accum, stats,
                        sample_begin, sample_count, counters, stream);
+}
+
+// ------------------------------------------------------------- include/ptmi_wf_tiles.h
+int ptmi_wf_render_tiles_stats(const ptmi_scene_view* scene, const ptmi_frame* frame, void* workspace,
+                               size_t workspace_bytes, float* accum, float* stats, const int32_t* tile_list,
+                               int32_t n_tiles, int32_t sample_begin, int32_t sample_count, uint64_t* counters,
+                               void* stream) {
+  return render_ws_any("wf_render_tiles_stats", kWfTilesStats, scene, frame, workspace, workspace_bytes, accum, stats,
+                       sample_begin, sample_count, counters, stream, tile_list, n_tiles);
 }
 
 int ptmi_tile_update(const ptmi_frame* frame, const float* stats, float threshold, int32_t min_spp, int32_t max_spp,

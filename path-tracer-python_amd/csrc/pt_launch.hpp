@@ -75,9 +75,13 @@ hipError_t mk_trace_staged(const DevScene& sc, const DevFrame& fr, int32_t stack
                            const int32_t* tile_list, int32_t n, int32_t s_begin, int32_t nb,
                            unsigned long long* counters, hipStream_t stream);
 // stats != nullptr: every batch resolves through launch_stats_resolve.
+// tile_list != nullptr (needs stats and n_list >= 1): tile-listed batches,
+// which trace, stage and resolve the pixels of tile_list[0 .. n_list) only
+// (device ids of the frame's tile grid, ids outside the grid ignored).
 hipError_t wf_render(const DevScene& sc, const DevFrame& fr, int32_t stack_needed, void* ws, size_t ws_bytes,
                      float* accum, int32_t s_begin, int32_t s_count, unsigned long long* counters,
-                     hipStream_t stream, float* stats = nullptr);
+                     hipStream_t stream, float* stats = nullptr, const int32_t* tile_list = nullptr,
+                     int32_t n_list = 0);
 // Sets the wavefront tail threshold (capacity / divisor; 0 = no tail launch); returns the previous one.
 int32_t wf_set_drain_at(int32_t divisor);
 // accum[pixel] += staging[s][p] for s = 0..batch-1 in order (profiled as `prof_kind`).

@@ -75,6 +75,12 @@
 //     order, as the reference's per-sample accumulation, with no atomics and
 //     no ordering constraint between concurrent paths of one pixel. Which
 //     ray is traced in which lane, and when, therefore changes nothing.
+//   * TILE-LISTED BATCHES (include/ptmi_wf_tiles.h): the LISTED
+//     instantiations of the queue kernels decode a work item through a list
+//     of the frame's 64-pixel tiles instead of the pixel set's 8x8 squares
+//     (decode_item, WfList), so an adaptive pass traces, stages and resolves
+//     the listed tiles only. Everything behind the decode is shared; the
+//     unlisted kernels carry no list and no branch for it.
 #include "pt_launch.hpp"
 #include "pt_prof.hpp"
 
@@ -251,7 +257,53 @@ struct Item {
   int32_t srel, p, px, py;
   bool valid;
 };
-__device__ __forceinline__ Item decode_item(const DevFrame& fr, const WfBufs& wb, uint32_t k) {
+// Tile-listed batches (the LISTED kernels; wf_plan with a tile list): a chunk
+// is one listed 64-pixel tile x csamp samples. Chunk c is virtual tile
+// v = c % n_list of sample block c / n_list (WfBufs::nsq holds n_list), the
+// frame tile is tiles[v], and item j of the chunk is that tile's lane j % 64
+// in the frame's tile grid (tile_grid, pt_mk_plan.hpp: row lane >> tw_log2,
+// column lane & (tw - 1) of the tile; WfBufs::sq_x holds its tiles per row) —
+// the pixels the tile id names in ptmi_tile_update, the listed megakernel and
+// the listed stats resolve. An id outside [0, ntiles) makes the chunk's 64
+// lanes invalid, like items outside the frame. The unlisted kernels carry no
+// list: WfList<false> is empty and never a kernel argument.
+template <bool LISTED>
+struct WfList {};
+template <>
+struct WfList<true> {
+  const int32_t* tiles;  // device, n_list ids
+  int32_t ntiles;        // tiles of the frame's grid
+  int32_t tw_log2;       // tile width log2 (3: 8x8, 4: 16x4, 5: 32x2, 6: 64x1)
+};
+template <bool LISTED>
+__device__ __forceinline__ WfList<LISTED> wf_list() {
+  return {};
+}
+template <bool LISTED>
+__device__ __forceinline__ WfList<LISTED> wf_list(const WfList<LISTED>& tl) {
+  return tl;
+}
+
+__device__ __forceinline__ Item decode_item(const DevFrame& fr, const WfBufs& wb, const WfList<true>& tl, uint32_t k) {
+  Item it;
+  const uint32_t per = 64u * (uint32_t)wb.csamp;
+  const uint32_t c = fdiv(k, wb.by_per), j = k - c * per;
+  const uint32_t blk = fdiv(c, wb.by_nsq), v = c - blk * (uint32_t)wb.nsq;  // v < n_list
+  const int32_t id = s_load(tl.tiles + v);
+  const bool in_grid = (uint32_t)id < (uint32_t)tl.ntiles;
+  const uint32_t t = in_grid ? (uint32_t)id : 0u;  // (< 2^31: FastDiv's range)
+  const int32_t ty = (int32_t)fdiv(t, wb.by_sqx), tx = (int32_t)t - ty * wb.sq_x;
+  const uint32_t lane = j & 63u;
+  const int32_t lx = (tx << tl.tw_log2) + (int32_t)(lane & ((1u << tl.tw_log2) - 1u));
+  const int32_t lr = ty * (64 >> tl.tw_log2) + (int32_t)(lane >> tl.tw_log2);
+  it.srel = (int32_t)blk * wb.csamp + (int32_t)(j >> 6);
+  it.valid = in_grid && lx < fr.w && lr < fr.n_rows && it.srel < wb.batch;
+  it.p = lr * fr.w + lx;
+  it.px = fr.x0 + lx;
+  it.py = it.valid ? frame_row(fr, lr) : 0;
+  return it;
+}
+__device__ __forceinline__ Item decode_item(const DevFrame& fr, const WfBufs& wb, const WfList<false>&, uint32_t k) {
   Item it;
   // multiply-shift divisions (exact: items < 2^31, FastDiv)
   const uint32_t per = 64u * (uint32_t)wb.csamp;
@@ -276,12 +328,14 @@ __device__ __forceinline__ uint32_t path_key(const DevFrame& fr, const WfBufs& w
 // stored) is regenerated from its item: the same get_ray draws
 // (kernels.py:1219-1239, direction unnormalized, Q1), throughput 1, depth and
 // wave 0.
-__device__ __forceinline__ Ray load_ray(const DevFrame& fr, const WfBufs& wb, const RayBuf& X, int32_t p, Item& it) {
+template <bool LISTED>
+__device__ __forceinline__ Ray load_ray(const DevFrame& fr, const WfBufs& wb, const WfList<LISTED>& tl, const RayBuf& X,
+                                        int32_t p, Item& it) {
   Ray r;
   const uint32_t w = s_load(X.item + p);
   r.fresh = (w & kFresh) != 0u;
   r.item = w & ~kFresh;
-  it = decode_item(fr, wb, r.item);
+  it = decode_item(fr, wb, tl, r.item);
   if (r.fresh) {
     // (storing it in wf_intersect instead, 28 B, measured 1-2 % slower on C3 in round 4)
     Rng rng{path_key(fr, wb, it), 0u};
@@ -301,8 +355,10 @@ __device__ __forceinline__ Ray load_ray(const DevFrame& fr, const WfBufs& wb, co
   return r;
 }
 
-__device__ __forceinline__ void stage(const DevFrame& fr, const WfBufs& wb, uint32_t k, pt_v3 c) {
-  const Item it = decode_item(fr, wb, k);
+template <bool LISTED>
+__device__ __forceinline__ void stage(const DevFrame& fr, const WfBufs& wb, const WfList<LISTED>& tl, uint32_t k,
+                                      pt_v3 c) {
+  const Item it = decode_item(fr, wb, tl, k);
   float* p = wb.staging + 3 * ((size_t)it.srel * (size_t)wb.npix + (size_t)it.p);
   s_store(p, c.x);
   s_store(p + 1, c.y);
@@ -469,8 +525,10 @@ __device__ __forceinline__ void append_cont(const WfBufs& wb, int32_t npar, int3
 // (kernels.py:1365-1375). w = the ray's item word (a fresh camera ray's
 // throughput is 1: no C record was stored for it), ref = the hit's leaf code,
 // 0 for a miss. Its one colour goes to the staging slot.
+template <bool LISTED>
 __device__ __forceinline__ void end_unscattered(const DevScene& sc, const DevFrame& fr, const WfBufs& wb,
-                                                const RayBuf& X, int32_t p, uint32_t w, int32_t ref) {
+                                                const WfList<LISTED>& tl, const RayBuf& X, int32_t p, uint32_t w,
+                                                int32_t ref) {
   pt_v3 thr = pt_v3f(1.0f, 1.0f, 1.0f);
   if (!(w & kFresh)) {
     const float4 c = q_load(X.c + p);
@@ -481,7 +539,7 @@ __device__ __forceinline__ void end_unscattered(const DevScene& sc, const DevFra
     const float4 e = sc.mats[5 * mat_index(sc, ref) + 1];  // emit colour (Mat::m1)
     col = (e.x > 0.0f || e.y > 0.0f || e.z > 0.0f) ? pt_mul(thr, pt_v3f(e.x, e.y, e.z)) : pt_v3f(0.0f, 0.0f, 0.0f);
   }
-  stage(fr, wb, w & ~kFresh, col);
+  stage(fr, wb, tl, w & ~kFresh, col);
 }
 
 // Closest-hit classes (PTMI_CLASS_*, include/ptmi.h) are packed into the
@@ -512,9 +570,13 @@ __device__ __forceinline__ void append_list(const WfBufs& wb, int32_t par, int32
 // fresh camera rays that fill the pipe back up to `capacity` while the pool
 // lasts. Writes the hit record (8 B) and one list entry (4 B) per ray; a path
 // end reads thr (16 B) and writes its staging slot.
-template <int STACK, int TRAV = PTMI_TRAV_STACK>
+// LISTED: a tile-listed batch; the kernel then takes one trailing argument,
+// the WfList<true> of its decode (the unlisted kernels' arguments are unchanged).
+template <int STACK, int TRAV = PTMI_TRAV_STACK, bool LISTED = false, class... List>
 __global__ __launch_bounds__(kWfBlock, stress_waves(isect_min_waves<STACK, TRAV>())) void wf_intersect(DevScene sc, DevFrame fr, WfBufs wb, int32_t par,
-                                                       unsigned long long* __restrict__ counters) {
+                                                       unsigned long long* __restrict__ counters, List... lst) {
+  static_assert(sizeof...(List) == (LISTED ? 1 : 0), "a listed kernel takes its WfList<true>, an unlisted one nothing");
+  const WfList<LISTED> tl = wf_list<LISTED>(lst...);
   constexpr int LDS = isect_lds<STACK, TRAV>();
   __shared__ uint2 lds_stack[LDS * kWfBlock];
   const int tid = threadIdx.x;
@@ -552,7 +614,7 @@ __global__ __launch_bounds__(kWfBlock, stress_waves(isect_min_waves<STACK, TRAV>
       const int32_t f = w0 - T.fresh_start + lane_id();
       const int32_t k = claim_items(wb, shard, f < nfresh);
       if (k >= 0) {
-        const Item it = decode_item(fr, wb, (uint32_t)k);
+        const Item it = decode_item(fr, wb, tl, (uint32_t)k);
         if (it.valid) {  // (padding items of squares past the frame / batch are skipped)
           Rng rng{path_key(fr, wb, it), 0u};
           get_ray(fr, it.px, it.py, rng, o, d);  // direction left unnormalized (Q1)
@@ -571,7 +633,7 @@ __global__ __launch_bounds__(kWfBlock, stress_waves(isect_min_waves<STACK, TRAV>
       if (!hit) ref = 0;  // a miss: no leaf code
       list = hit ? leaf_class(ref) : kListEnded;
       if (list == kListEnded) {
-        end_unscattered(sc, fr, wb, X, p, item, ref);
+        end_unscattered(sc, fr, wb, tl, X, p, item, ref);
         ++n_ended;
         list = -1;
       } else {
@@ -625,8 +687,10 @@ __device__ __forceinline__ bool scatter_epilogue(const DevFrame& fr, bool scatte
 // Per-lane tail of a path a scatter ended: stage its colour (0 unless it
 // ended on an emissive boundary fallback; misses and emissive surface hits
 // end in wf_intersect, end_unscattered).
-__device__ __forceinline__ void finish_ended(const DevFrame& fr, const WfBufs& wb, const Ray& ray, pt_v3 emit) {
-  stage(fr, wb, ray.item,
+template <bool LISTED>
+__device__ __forceinline__ void finish_ended(const DevFrame& fr, const WfBufs& wb, const WfList<LISTED>& tl,
+                                             const Ray& ray, pt_v3 emit) {
+  stage(fr, wb, tl, ray.item,
         (emit.x > 0.0f || emit.y > 0.0f || emit.z > 0.0f) ? pt_mul(ray.thr, emit) : pt_v3f(0.0f, 0.0f, 0.0f));
 }
 
@@ -657,13 +721,14 @@ __device__ __forceinline__ int32_t list_counts(const WfBufs& wb, int32_t par, in
 // The ray at position p of the Lambertian, glossy or dielectric list
 // (`list`, wave-uniform): shade_and_scatter for a surface hit
 // (kernels.py:1359-1399). A continuing ray goes to cn.
+template <bool LISTED>
 __device__ __forceinline__ void shade_entry(const DevScene& sc, const DevFrame& fr, const WfBufs& wb,
-                                            const RayBuf& X, int32_t list, int32_t p, uint32_t& n_ended,
-                                            uint32_t (&ends)[2], Cont& cn) {
+                                            const WfList<LISTED>& tl, const RayBuf& X, int32_t list, int32_t p,
+                                            uint32_t& n_ended, uint32_t (&ends)[2], Cont& cn) {
   const float2 h = h_load(X.hit + p);
   const int32_t ref = __float_as_int(h.y);
   Item it;
-  const Ray ray = load_ray(fr, wb, X, p, it);
+  const Ray ray = load_ray(fr, wb, tl, X, p, it);
   const Mat m = load_mat(sc, mat_index(sc, ref));
   Rng r{path_key(fr, wb, it), ray.ctr};
   const pt_v3 hp = pt_add(ray.o, pt_scale(ray.d, h.x));
@@ -679,7 +744,7 @@ __device__ __forceinline__ void shade_entry(const DevScene& sc, const DevFrame& 
     sc_ok = scatter(sc, ref, m, ray.d, hp, nrm, r, sdir, att);
   }
   if (!scatter_epilogue(fr, sc_ok, hp, sdir, att, ray, r, ends, cn)) {
-    finish_ended(fr, wb, ray, emitted(m));
+    finish_ended(fr, wb, tl, ray, emitted(m));
     ++n_ended;
   }
 }
@@ -688,16 +753,16 @@ __device__ __forceinline__ void shade_entry(const DevScene& sc, const DevFrame& 
 // flight, apply_constant_medium kernels.py:365-450, and the volume branch of
 // shade_and_scatter, kernels.py:1326-1357) or, is_noise, of the Perlin list.
 // A continuing ray (a scatter, or a passthrough at the same depth) goes to cn.
-template <int STACK, int TRAV>
-__device__ __forceinline__ void medium_entry(const DevScene& sc, const DevFrame& fr, const WfBufs& wb, Stack st,
-                                             const RayBuf& X, int32_t p, bool is_noise, uint32_t& n_ended,
-                                             uint32_t (&ends)[2], Cont& cn) {
+template <int STACK, int TRAV, bool LISTED>
+__device__ __forceinline__ void medium_entry(const DevScene& sc, const DevFrame& fr, const WfBufs& wb,
+                                             const WfList<LISTED>& tl, Stack st, const RayBuf& X, int32_t p,
+                                             bool is_noise, uint32_t& n_ended, uint32_t (&ends)[2], Cont& cn) {
   bool go = false;
   pt_v3 emit = pt_v3f(0.0f, 0.0f, 0.0f);
   const float2 h = h_load(X.hit + p);
   const int32_t ref = __float_as_int(h.y);
   Item it;
-  const Ray ray = load_ray(fr, wb, X, p, it);
+  const Ray ray = load_ray(fr, wb, tl, X, p, it);
   float te = 0.0f;
   int32_t rex = 0;
   bool hx = false;
@@ -749,7 +814,7 @@ __device__ __forceinline__ void medium_entry(const DevScene& sc, const DevFrame&
   }
   if (!passthrough) go = scatter_epilogue(fr, scattered, hp, sdir, att, ray, r, ends, cn);
   if (!go) {
-    finish_ended(fr, wb, ray, emit);
+    finish_ended(fr, wb, tl, ray, emit);
     ++n_ended;
   }
 }
@@ -784,9 +849,12 @@ __device__ __forceinline__ void medium_entry(const DevScene& sc, const DevFrame&
 // (profiles/r04/ab/ab_r04i_split_knobs_ruv.log).
 constexpr int32_t kScatterOrder[kLists] = {kListMedium, kListNoise, kListLambertian, kListGlossy, kListDielectric};
 
-template <int STACK, int TRAV = PTMI_TRAV_STACK>
+template <int STACK, int TRAV = PTMI_TRAV_STACK, bool LISTED = false, class... List>
 __global__ __launch_bounds__(kWfBlock, stress_waves(PTMI_WF_SCATTER_MIN_WAVES)) void wf_scatter(DevScene sc, DevFrame fr, WfBufs wb,
-                                                    int32_t par, unsigned long long* __restrict__ counters) {
+                                                    int32_t par, unsigned long long* __restrict__ counters,
+                                                    List... lst) {
+  static_assert(sizeof...(List) == (LISTED ? 1 : 0), "a listed kernel takes its WfList<true>, an unlisted one nothing");
+  const WfList<LISTED> tl = wf_list<LISTED>(lst...);
   __shared__ uint2 lds_stack[STACK * kWfBlock];
   Stack st{lds_stack + threadIdx.x};
   const RayBuf& X = wb.rb[par];
@@ -835,9 +903,9 @@ __global__ __launch_bounds__(kWfBlock, stress_waves(PTMI_WF_SCATTER_MIN_WAVES)) 
     cn.go = false;
     if (p >= 0) {  // (p < 0: the list's padding)
       if (lid == kListMedium || lid == kListNoise)
-        medium_entry<STACK, TRAV>(sc, fr, wb, st, X, p, lid == kListNoise, n_ended, ends, cn);
+        medium_entry<STACK, TRAV>(sc, fr, wb, tl, st, X, p, lid == kListNoise, n_ended, ends, cn);
       else
-        shade_entry(sc, fr, wb, X, lid, p, n_ended, ends, cn);
+        shade_entry(sc, fr, wb, tl, X, lid, p, n_ended, ends, cn);
     }
     append_cont(wb, par ^ 1, shard, cn);
   }
@@ -859,7 +927,7 @@ __device__ __noinline__
 #else
 __device__ __forceinline__
 #endif
-void wf_trace(const DevFrame& fr, const WfBufs& wb, uint32_t item, uint32_t meta,
+void wf_trace(const DevFrame& fr, const WfBufs& wb, const WfList<false>& tl, uint32_t item, uint32_t meta,
                                       uint32_t ctr, float t, int32_t ref, uint32_t go, const Cont& cn) {
   const uint32_t k = atomicAdd(&g_wf_trace_n, 1u);
   if (k >= kTraceCap) return;
@@ -877,7 +945,7 @@ void wf_trace(const DevFrame& fr, const WfBufs& wb, uint32_t item, uint32_t meta
     r[9] = __float_as_uint(cn.thr.y);
     r[10] = __float_as_uint(cn.thr.z);
   } else {
-    const Item it = decode_item(fr, wb, item);
+    const Item it = decode_item(fr, wb, tl, item);
     const float* c = wb.staging + 3 * ((size_t)it.srel * (size_t)wb.npix + (size_t)it.p);
     r[6] = 0xffffffffu;
     r[7] = 0xffffffffu;
@@ -893,10 +961,11 @@ void wf_trace(const DevFrame& fr, const WfBufs& wb, uint32_t item, uint32_t meta
 // 1242-1263), the classification of wf_intersect and the shading of
 // wf_scatter (the same entry functions); the continuing ray is stored back in
 // place. Returns whether the path goes on.
-template <int STACK, int TRAV>
-__device__ __forceinline__ bool drain_segment(const DevScene& sc, const DevFrame& fr, const WfBufs& wb, Stack st,
-                                              const RayBuf& X, int32_t p, uint32_t& n_seg, uint32_t& n_med,
-                                              uint32_t& n_ended, uint32_t (&ends)[2]) {
+template <int STACK, int TRAV, bool LISTED>
+__device__ __forceinline__ bool drain_segment(const DevScene& sc, const DevFrame& fr, const WfBufs& wb,
+                                              const WfList<LISTED>& tl, Stack st, const RayBuf& X, int32_t p,
+                                              uint32_t& n_seg, uint32_t& n_med, uint32_t& n_ended,
+                                              uint32_t (&ends)[2]) {
   const float4 a = q_load(X.a + p);
   const float2 dyz = h_load(X.d + p);
 #if PTMI_WF_TRACE
@@ -914,16 +983,16 @@ __device__ __forceinline__ bool drain_segment(const DevScene& sc, const DevFrame
   Cont cn;
   cn.go = false;
   if (list == kListEnded) {
-    end_unscattered(sc, fr, wb, X, p, s_load(X.item + p), ref);
+    end_unscattered(sc, fr, wb, tl, X, p, s_load(X.item + p), ref);
     ++n_ended;
   } else if (list == kListMedium || list == kListNoise) {
     n_med += list == kListMedium ? 1u : 0u;
-    medium_entry<STACK, TRAV>(sc, fr, wb, st, X, p, list == kListNoise, n_ended, ends, cn);
+    medium_entry<STACK, TRAV>(sc, fr, wb, tl, st, X, p, list == kListNoise, n_ended, ends, cn);
   } else {
-    shade_entry(sc, fr, wb, X, list, p, n_ended, ends, cn);
+    shade_entry(sc, fr, wb, tl, X, list, p, n_ended, ends, cn);
   }
 #if PTMI_WF_TRACE
-  wf_trace(fr, wb, tr_item, tr_meta, tr_ctr, t, ref, cn.go ? 1u : 0u, cn);
+  if constexpr (!LISTED) wf_trace(fr, wb, tl, tr_item, tr_meta, tr_ctr, t, ref, cn.go ? 1u : 0u, cn);
 #endif
   if (cn.go) store_ray(X, p, cn);
   return cn.go;  // false: the path ended (its colour is staged)
@@ -945,9 +1014,11 @@ __device__ __forceinline__ bool drain_segment(const DevScene& sc, const DevFrame
 #ifndef PTMI_WF_DRAIN_MIN_WAVES
 #define PTMI_WF_DRAIN_MIN_WAVES 1
 #endif
-template <int STACK, int TRAV = PTMI_TRAV_STACK>
+template <int STACK, int TRAV = PTMI_TRAV_STACK, bool LISTED = false, class... List>
 __global__ __launch_bounds__(kWfBlock, stress_waves(PTMI_WF_DRAIN_MIN_WAVES)) void wf_drain(DevScene sc, DevFrame fr, WfBufs wb, int32_t par,
-                                                   unsigned long long* __restrict__ counters) {
+                                                   unsigned long long* __restrict__ counters, List... lst) {
+  static_assert(sizeof...(List) == (LISTED ? 1 : 0), "a listed kernel takes its WfList<true>, an unlisted one nothing");
+  const WfList<LISTED> tl = wf_list<LISTED>(lst...);
   __shared__ uint2 lds_stack[STACK * kWfBlock];
   Stack st{lds_stack + threadIdx.x};
   const RayBuf& X = wb.rb[par];
@@ -960,7 +1031,7 @@ __global__ __launch_bounds__(kWfBlock, stress_waves(PTMI_WF_DRAIN_MIN_WAVES)) vo
     const int32_t p = cont_position(T, wb, w0);  // (every lane active: cross-lane reads inside)
     if (p < 0) continue;
     // each lane loops over its own path until it ends
-    while (drain_segment<STACK, TRAV>(sc, fr, wb, st, X, p, n_seg, n_med, n_ended, ends)) {
+    while (drain_segment<STACK, TRAV>(sc, fr, wb, tl, st, X, p, n_seg, n_med, n_ended, ends)) {
     }
   }
   if (counters) {
@@ -1020,11 +1091,16 @@ std::atomic<int32_t> g_drain_at{PTMI_WF_DRAIN_AT};
 
 // One batch: generate on the caller's stream, fork the pipes, run each pipe's
 // intersect -> scatter loop on its own stream until its rays have all ended
-// and the pool is empty, join, resolve.
-template <int STACK, int TRAV = PTMI_TRAV_STACK>
+// and the pool is empty, join, resolve. LISTED: the plan is a tile-listed
+// one (wf_plan with the list), the kernels decode through the list and the
+// resolve (always the stats resolve) covers the listed tiles only.
+template <int STACK, int TRAV = PTMI_TRAV_STACK, bool LISTED = false>
 static hipError_t wf_batch(const DevScene& sc, const DevFrame& fr, const WfPlan& plan, float* accum,
                            unsigned long long* counters, hipStream_t stream, const PipeStreams& ps,
-                           float* stats) {
+                           float* stats, const int32_t* tile_list = nullptr, int32_t n_list = 0) {
+  const TileGrid tg = tile_grid(fr);
+  const WfList<true> tl{tile_list, tg.ntiles, tg.tw_log2};  // the listed kernels' trailing argument
+  (void)tl;
   const WfBufs* wbs = plan.wb;
   const int32_t batch = wbs[0].batch;
   const unsigned g = plan.grid, gd = plan.grid_drain;  // the pipes' iterations; the tail launch
@@ -1066,10 +1142,18 @@ static hipError_t wf_batch(const DevScene& sc, const DevFrame& fr, const WfPlan&
         const WfBufs& wb = wbs[p];
         const int32_t par = (int32_t)((it + j) & 1);  // which ray buffer and list counters this iteration uses
         const int ps_i = prof_begin(kProfWfIntersect, st[p]);
-        hipLaunchKernelGGL((wf_intersect<STACK, TRAV>), dim3(g), dim3(kWfBlock), 0, st[p], sc, fr, wb, par, counters);
+        if constexpr (LISTED)
+          hipLaunchKernelGGL((wf_intersect<STACK, TRAV, true>), dim3(g), dim3(kWfBlock), 0, st[p], sc, fr, wb, par,
+                             counters, tl);
+        else
+          hipLaunchKernelGGL((wf_intersect<STACK, TRAV>), dim3(g), dim3(kWfBlock), 0, st[p], sc, fr, wb, par, counters);
         prof_end(ps_i, st[p]);
         const int ps_s = prof_begin(kProfWfScatter, st[p]);
-        hipLaunchKernelGGL((wf_scatter<STACK, TRAV>), dim3(g), dim3(kWfBlock), 0, st[p], sc, fr, wb, par, counters);
+        if constexpr (LISTED)
+          hipLaunchKernelGGL((wf_scatter<STACK, TRAV, true>), dim3(g), dim3(kWfBlock), 0, st[p], sc, fr, wb, par,
+                             counters, tl);
+        else
+          hipLaunchKernelGGL((wf_scatter<STACK, TRAV>), dim3(g), dim3(kWfBlock), 0, st[p], sc, fr, wb, par, counters);
         prof_end(ps_s, st[p]);
       }
     }
@@ -1104,8 +1188,12 @@ static hipError_t wf_batch(const DevScene& sc, const DevFrame& fr, const WfPlan&
           // queued behind the iterations in flight, on the rays the next
           // iteration would trace
           const int pd = prof_begin(kProfWfDrain, st[p]);
-          hipLaunchKernelGGL((wf_drain<STACK, TRAV>), dim3(gd), dim3(kWfBlock), 0, st[p], sc, fr, wbs[p],
-                             (int32_t)(it & 1), counters);
+          if constexpr (LISTED)
+            hipLaunchKernelGGL((wf_drain<STACK, TRAV, true>), dim3(gd), dim3(kWfBlock), 0, st[p], sc, fr, wbs[p],
+                               (int32_t)(it & 1), counters, tl);
+          else
+            hipLaunchKernelGGL((wf_drain<STACK, TRAV>), dim3(gd), dim3(kWfBlock), 0, st[p], sc, fr, wbs[p],
+                               (int32_t)(it & 1), counters);
           prof_end(pd, st[p]);
           err = hipGetLastError();
           live[p] = false;
@@ -1131,6 +1219,9 @@ static hipError_t wf_batch(const DevScene& sc, const DevFrame& fr, const WfPlan&
     if (err == hipSuccess) err = e;
   }
   if (err != hipSuccess) return err;
+  if constexpr (LISTED)
+    return launch_stats_resolve(fr, wbs[0].staging, wbs[0].npix, batch, accum, stats, tile_list, n_list,
+                                kProfWfResolve, stream);
   if (stats)
     return launch_stats_resolve(fr, wbs[0].staging, wbs[0].npix, batch, accum, stats, nullptr, 0, kProfWfResolve,
                                 stream);
@@ -1164,9 +1255,11 @@ namespace ptmi {
 
 hipError_t wf_render(const DevScene& sc, const DevFrame& fr, int32_t stack_needed, void* ws, size_t ws_bytes,
                      float* accum, int32_t s_begin, int32_t s_count, unsigned long long* counters,
-                     hipStream_t stream, float* stats) {
+                     hipStream_t stream, float* stats, const int32_t* tile_list, int32_t n_list) {
+  if (tile_list && (!stats || n_list < 1)) return hipErrorInvalidValue;
   const int32_t batch =
-      fit_batch(s_count, wf_max_batch(fr), [&](int32_t b) { return wf_workspace_bytes(fr, b); }, ws_bytes);
+      fit_batch(s_count, tile_list ? wf_max_batch_listed(n_list) : wf_max_batch(fr),
+                [&](int32_t b) { return wf_workspace_bytes(fr, b); }, ws_bytes);
   if (batch < 1) return hipErrorInvalidValue;
   int dev = 0;
   {
@@ -1182,11 +1275,17 @@ hipError_t wf_render(const DevScene& sc, const DevFrame& fr, int32_t stack_neede
   }
   for (int32_t b0 = 0; b0 < s_count; b0 += batch) {
     const int32_t nb = s_count - b0 < batch ? s_count - b0 : batch;
-    const WfPlan plan = wf_plan(fr, nb, s_begin + b0, ws);
-    const hipError_t e = dispatch_traversal<false>(fr, stack_needed, [&](auto stack, auto trav) {
-      constexpr int S = decltype(stack)::value, T = decltype(trav)::value;
-      return wf_batch<S, T>(sc, fr, plan, accum, counters, stream, *ps, stats);
-    });
+    const WfPlan plan = wf_plan(fr, nb, s_begin + b0, ws, tile_list, n_list);
+    // the listed dispatch wraps the same ladder (as mk_trace_staged does): every
+    // traversal mode and stack rung has its listed kernels
+    auto run = [&](auto listed) {
+      return dispatch_traversal<false>(fr, stack_needed, [&](auto stack, auto trav) {
+        constexpr int S = decltype(stack)::value, T = decltype(trav)::value;
+        return wf_batch<S, T, decltype(listed)::value>(sc, fr, plan, accum, counters, stream, *ps, stats, tile_list,
+                                                       n_list);
+      });
+    };
+    const hipError_t e = !tile_list ? run(std::false_type{}) : run(std::true_type{});
     if (e != hipSuccess) return e;
   }
   return hipSuccess;

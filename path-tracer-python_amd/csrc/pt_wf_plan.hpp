@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "pt_device.hpp"
+#include "pt_mk_plan.hpp"
 
 namespace ptmi {
 
@@ -144,11 +145,27 @@ inline int64_t wf_max_batch(const DevFrame& fr) {
   const int64_t sq_items = 64ll * ((fr.w + 7) / 8) * ((fr.n_rows + 7) / 8);
   return sq_items > 0 ? (0x7fffffffll - (1ll << 24)) / sq_items - (PTMI_WF_CHUNK_SAMPLES - 1) : 0;
 }
+// The same limit for a tile-listed batch, whose items are 64 per listed tile
+// whatever the frame: nb <= (2^31 - 1 - 2^24) / (64 * n_list) - (chunk samples - 1).
+inline int64_t wf_max_batch_listed(int32_t n_list) {
+  return n_list > 0 ? (0x7fffffffll - (1ll << 24)) / (64ll * n_list) - (PTMI_WF_CHUNK_SAMPLES - 1) : 0;
+}
 
 // One batch of nb samples from s_begin in the workspace at ws: every pipe's
 // buffers and work-item fields, the grids, the host loop's iteration bound
 // and the workspace's size. The size depends on the frame's pixel count and
 // nb only (wf_workspace_bytes).
+//
+// tile_list != nullptr: a tile-listed batch. Its work items cover the n_list
+// listed 64-pixel tiles of the frame's tile grid (tile_grid, pt_mk_plan.hpp)
+// instead of the pixel set's 8x8 squares: chunk c is virtual tile c % n_list
+// of sample block c / n_list, and the kernels' LISTED decode reads the frame
+// tile from tile_list (WfList, pt_wavefront.hip). WfBufs::nsq / by_nsq then
+// hold n_list and sq_x / by_sqx the grid's tiles per row. Capacity, grids,
+// shard lengths and max_iters derive from the listed items (at most
+// min(npix, 64 * n_list) * nb paths are alive at once, so the ray buffers are
+// never larger than the unlisted batch's); staging stays [nb][npix], so every
+// region lies inside wf_workspace_bytes(fr, nb).
 struct WfPlan {
   WfBufs wb[kPipes];
   unsigned grid;        // wf_intersect / wf_scatter: a multiple of kShards, so block b's shard is b % kShards
@@ -159,10 +176,13 @@ struct WfPlan {
   int64_t max_iters;
   size_t total;
 };
-inline WfPlan wf_plan(const DevFrame& fr, int32_t nb, int32_t s_begin, void* ws) {
+inline WfPlan wf_plan(const DevFrame& fr, int32_t nb, int32_t s_begin, void* ws, const int32_t* tile_list = nullptr,
+                      int32_t n_list = 0) {
   WfPlan P{};
   const int32_t npix = fr.w * fr.n_rows;
-  const int64_t items = (int64_t)npix * nb;
+  const int64_t staged = (int64_t)npix * nb;  // staging slots: [sample][frame pixel], listed or not
+  int64_t items = staged;                     // paths of the batch
+  if (tile_list && 64ll * n_list < npix) items = 64ll * n_list * nb;
   // rays per iteration: 2^22 (or the batch's items if fewer), whatever the
   // frame size — the pool refills the buffers, so a 4K frame needs no more
   // (the ray buffers are 56 B x 12 positions per ray: 2.8 GB at 2^22)
@@ -184,13 +204,14 @@ inline WfPlan wf_plan(const DevFrame& fr, int32_t nb, int32_t s_begin, void* ws)
   const size_t lists_pipe = kListArrays * kShards * sizeof(int32_t) * (size_t)medseg;
   const size_t lists = kPipes * rb_pipe;
   const size_t staging = (lists + kPipes * lists_pipe + 255) & ~(size_t)255;
-  const size_t spill = (staging + 3 * sizeof(float) * (size_t)items + 255) & ~(size_t)255;
+  const size_t spill = (staging + 3 * sizeof(float) * (size_t)staged + 255) & ~(size_t)255;
   const size_t ctl = spill + kPipes * kSpillPipeBytes;
   P.total = ctl + kCtlWords * sizeof(int32_t);
 
   // the pixel set's 8x8 squares and the batch's chunks (in 64 bits: a size
   // query may ask for more samples than wf_max_batch allows)
-  const int32_t sq_x = (fr.w + 7) / 8, nsq = sq_x * ((fr.n_rows + 7) / 8);
+  const int32_t sq_x = tile_list ? tile_grid(fr).tiles_x : (fr.w + 7) / 8;
+  const int32_t nsq = tile_list ? n_list : sq_x * ((fr.n_rows + 7) / 8);
   const int32_t csamp = nb < PTMI_WF_CHUNK_SAMPLES ? nb : PTMI_WF_CHUNK_SAMPLES;
   const int64_t nchunks = csamp > 0 ? (int64_t)nsq * ((nb + csamp - 1) / csamp) : 0;
   const uintptr_t base = (uintptr_t)ws;  // integer arithmetic: a size query carves from a null base

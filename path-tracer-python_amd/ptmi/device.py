@@ -14,7 +14,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib, guide, post, temporal
+from . import _lib, guide, post, temporal, wf_tiles
 from .scene_data import DeviceLayout, SceneArrays, camera_upload, pack_device
 
 
@@ -365,6 +365,16 @@ class Integrator:
         with self._dev():
             self._call('ptmi_stats_clear', frame, stats.data_ptr(), self._stream(stream))
 
+    def _check_tiles(self, tiles):
+        """(tensor or None, count) of a ``tiles`` argument: None, or (int32 device tensor of tile ids, count)."""
+        tl, nt = (None, 0) if tiles is None else tiles
+        if tl is not None:
+            nt = int(nt)
+            if not (isinstance(tl, torch.Tensor) and tl.dtype == torch.int32 and tl.is_contiguous()
+                    and tl.device == self.scene.device and 0 <= nt <= tl.numel()):
+                raise _lib.PtmiError('tiles must be (contiguous int32 tensor on the scene device, count <= its length)')
+        return tl, nt
+
     def render_mk_stats(self, frame, accum, stats, sample_begin, sample_count, tiles=None, stream=None):
         """Megakernel samples [sample_begin, sample_begin + sample_count) added
         into accum in sample order and into stats (Welford on the luminance):
@@ -374,12 +384,7 @@ class Integrator:
         _check_accum(accum, frame, self.scene.device)
         _check_stats(stats, frame.height, frame.width, self.scene.device)
         sample_count = int(sample_count)
-        tl, nt = (None, 0) if tiles is None else tiles
-        if tl is not None:
-            nt = int(nt)
-            if not (isinstance(tl, torch.Tensor) and tl.dtype == torch.int32 and tl.is_contiguous()
-                    and tl.device == self.scene.device and 0 <= nt <= tl.numel()):
-                raise _lib.PtmiError('tiles must be (contiguous int32 tensor on the scene device, count <= its length)')
+        tl, nt = self._check_tiles(tiles)
         npix = frame.w * len(frame_pixel_rows(frame))
         if npix == 0 or sample_count <= 0 or (tl is not None and nt == 0):
             return
@@ -399,12 +404,24 @@ class Integrator:
                 self._call('ptmi_mk_resolve_stats_ws', frame, wp, self._ws_bytes, accum.data_ptr(), stats.data_ptr(),
                            tp, nt, n, sp)
 
-    def render_wf_stats(self, frame, accum, stats, sample_begin, sample_count, stream=None):
-        """render_wf resolving through the stats resolve (whole frame only)."""
+    def render_wf_stats(self, frame, accum, stats, sample_begin, sample_count, tiles=None, stream=None):
+        """render_wf resolving through the stats resolve. ``tiles``: None for
+        the whole frame, or (int32 device tensor of tile ids, count): only
+        those tiles are traced and resolved (ptmi_wf_render_tiles_stats,
+        include/ptmi_wf_tiles.h); an empty list returns at once."""
         _check_accum(accum, frame, self.scene.device)
         _check_stats(stats, frame.height, frame.width, self.scene.device)
+        tl, nt = self._check_tiles(tiles)
+        if tl is not None and nt == 0:
+            return
         with self._dev():
             ws = self.workspace(frame, sample_count)
+            if tl is not None:
+                _lib.check(wf_tiles.load().ptmi_wf_render_tiles_stats(
+                    self.scene.view, frame, ws.data_ptr(), self._ws_bytes, accum.data_ptr(), stats.data_ptr(),
+                    tl.data_ptr(), nt, int(sample_begin), int(sample_count), self._cnt(), self._stream(stream)),
+                    'ptmi_wf_render_tiles_stats')
+                return
             self._call('ptmi_wf_render_stats', self.scene.view, frame, ws.data_ptr(), self._ws_bytes,
                        accum.data_ptr(), stats.data_ptr(), int(sample_begin), int(sample_count), self._cnt(),
                        self._stream(stream))

@@ -217,7 +217,7 @@ class MI355XRenderer:
         self.denoised = self.denoised_var = self.denoise_seconds = None  # of the render this one replaces
 
     def render_adaptive(self, target_error, pass_spp=None, min_spp=16, max_spp=None, integrator='megakernel',
-                        resume=False, enable_preview: bool = True):
+                        resume=False, enable_preview: bool = True, tiles=None):
         """Adaptive render (no counterpart in the reference, which always runs
         cam.samples_per_pixel samples of every pixel). Pass k renders samples
         [k * pass_spp, (k + 1) * pass_spp) of the tiles still active, through
@@ -226,13 +226,23 @@ class MI355XRenderer:
         error (the mean relative standard error of its pixels' luminance) is
         at most target_error, or at max_spp samples (default
         cam.samples_per_pixel). Stops when no tile is active. A tile whose
-        error is NaN (a NaN sample) is done. integrator='wavefront' renders the
-        whole frame every pass; only the stop is adaptive. Single device only
-        (band_stride == 1). The image divides each pixel by its own sample
-        count. resume=True continues a load_checkpoint() state bit-identically."""
+        error is NaN (a NaN sample) is done. ``tiles``: whether a pass traces
+        the active tiles only. None is each integrator's default: the
+        megakernel lists, integrator='wavefront' renders the whole frame every
+        pass and only its stop is adaptive. integrator='wavefront', tiles=True
+        passes the active list to the wavefront once fewer than all tiles are
+        active (Integrator.render_wf_stats, include/ptmi_wf_tiles.h); the
+        megakernel always lists, so tiles=False with it is a ValueError.
+        Single device only (band_stride == 1). The image divides each pixel by
+        its own sample count. resume=True continues a load_checkpoint() state bit-identically."""
         import torch
         if integrator not in ('megakernel', 'wavefront'):
             raise ValueError(f'unknown integrator {integrator!r}')
+        mk = integrator == 'megakernel'
+        if mk and tiles is not None and not tiles:
+            raise ValueError("render_adaptive(integrator='megakernel') always traces the listed tiles: tiles=False "
+                             'is not available')
+        listed = mk or bool(tiles)
         self._integrator_label = 'adaptive-' + integrator
         self._upload_camera()
         if self.frame.band_stride != 1:
@@ -243,9 +253,9 @@ class MI355XRenderer:
         target_error = float(np.float32(target_error))
         if not target_error >= 0.0 or pass_spp < 1 or min_spp < 0 or max_spp < min_spp:
             raise ValueError('render_adaptive needs target_error >= 0, pass_spp >= 1 and 0 <= min_spp <= max_spp')
-        self._adaptive = {'target_error': target_error, 'pass_spp': pass_spp, 'min_spp': min_spp, 'max_spp': max_spp}
+        self._adaptive = {'target_error': target_error, 'pass_spp': pass_spp, 'min_spp': min_spp, 'max_spp': max_spp,
+                          'listed': listed}
         integ = self.integrator
-        mk = integrator == 'megakernel'
         t0 = time.time()
         if resume:
             if self._resume_state is None:
@@ -272,17 +282,15 @@ class MI355XRenderer:
             n = min(pass_spp, max_spp - self.current_sample)
             active = tiles['n']
             t = time.time()
-            if mk:
-                integ.render_mk_stats(self.frame, self.accum, self.stats, self.current_sample, n,
-                                      None if active == ntiles else (tiles['list'], active))
-            else:
-                integ.render_wf_stats(self.frame, self.accum, self.stats, self.current_sample, n)
+            sel = (tiles['list'], active) if listed and active < ntiles else None
+            (integ.render_mk_stats if mk else integ.render_wf_stats)(self.frame, self.accum, self.stats,
+                                                                     self.current_sample, n, sel)
             integ.tile_update(self.frame, self.stats, target_error, min_spp, max_spp, tiles)
             torch.cuda.synchronize(self.dscene.device)
             dt = time.time() - t
             self.sample_times += [dt / n] * n
             self.current_sample += n
-            traced = (64 * active if mk else self.cam.img_width * self.cam.img_height) * n
+            traced = (64 * active if listed else self.cam.img_width * self.cam.img_height) * n
             self.adaptive_passes.append({'pass': len(self.adaptive_passes), 'active_tiles': active, 'samples': n,
                                          'traced': traced, 'seconds': dt, 'active_after': tiles['n']})
             print(f'pass {len(self.adaptive_passes):3d} | {self.current_sample:5d}/{max_spp} spp | '
@@ -443,7 +451,8 @@ class MI355XRenderer:
             a = self._adaptive
             st.update(stats=self.stats.cpu().numpy(), tile_state=self._tiles['state'].cpu().numpy(),
                       tile_err=self._tiles['err'].cpu().numpy(),
-                      adaptive=np.array([a['target_error'], a['pass_spp'], a['min_spp'], a['max_spp']], np.float64),
+                      adaptive=np.array([a['target_error'], a['pass_spp'], a['min_spp'], a['max_spp'],
+                                         float(a['listed'])], np.float64),
                       adaptive_passes=np.array([[q['active_tiles'], q['samples'], q['traced'], q['active_after']]
                                                 for q in self.adaptive_passes], np.int64).reshape(-1, 4),
                       adaptive_seconds=np.array([q['seconds'] for q in self.adaptive_passes], np.float64))
@@ -487,6 +496,9 @@ class MI355XRenderer:
             ids = np.flatnonzero(ad['tile_state']).astype(np.int32)
             lst = np.zeros(ad['tile_state'].size, np.int32)
             lst[:ids.size] = ids
+            if ad['adaptive'].size == 4:  # written before the tiles flag: the integrator's default
+                default = str(state['integrator']) == 'adaptive-megakernel'
+                ad['adaptive'] = np.append(ad['adaptive'], float(default))
             self._resume_state['adaptive'] = ad['adaptive']
             self._resume_tiles = {'state': torch.from_numpy(ad['tile_state'].astype(np.int32)).to(dev),
                                   'err': torch.from_numpy(ad['tile_err'].astype(np.float32)).to(dev),
@@ -504,7 +516,8 @@ class MI355XRenderer:
             raise ValueError('checkpoint accumulator does not match the image size')
         if self._is_adaptive():  # the adaptive parameters and the tile grid must match too
             a = self._adaptive
-            want = np.array([a['target_error'], a['pass_spp'], a['min_spp'], a['max_spp']], np.float64)
+            want = np.array([a['target_error'], a['pass_spp'], a['min_spp'], a['max_spp'], float(a['listed'])],
+                            np.float64)
             if not np.array_equal(want, self._resume_state.get('adaptive')):
                 raise ValueError('checkpoint was written for another render: adaptive differs')
             _, _, tx, ty = self.integrator.tile_grid(self.frame)
