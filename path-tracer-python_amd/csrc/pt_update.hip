@@ -1,0 +1,250 @@
+// pt_update.hip — the scene-update ABI (include/ptmi_update.h): primitives
+// moved in place and the BVH refitted above them.
+//
+//   * upd_leaves: one lane per edit of the three lists: the primitive row is
+//     copied and the leaf box, computed from the builder-form record, is
+//     written into ref_nodes. An edit whose ids are out of range, or whose leaf
+//     does not hold that primitive, is skipped.
+//   * upd_refit: one launch per level of internal nodes, deepest first, one
+//     lane per node: the union of the two children's boxes goes to ref_nodes
+//     and both children's boxes and centres go to the node's 80-B row. The
+//     levels are ordered by the kernel boundary on the stream: the per-XCD L2s
+//     are not coherent with each other within a launch, so a level written by
+//     one launch is read by the next and by no lane of its own.
+//   * upd_refit_one (PTMI_UPDATE_ONE_GROUP): the same refit as one launch of
+//     one 1024-lane workgroup that walks the levels behind __syncthreads();
+//     faster on trees of a few thousand nodes, chosen by the caller.
+//   * upd_root: ref_nodes[0]'s box to the caller's float[6].
+//
+// The arithmetic is pt_update_math.hpp's, shared with update_check.cpp. A few
+// thousand lanes of min / max: no LDS, no cross-lane reads, nothing timed by
+// ptmi_prof_*. No render kernel is involved.
+#include <hip/hip_runtime.h>
+
+#include "../../include/ptmi.h"
+#include "../../include/ptmi_update.h"
+#include "pt_update_math.hpp"
+
+namespace ptmi {
+
+int set_last_error(int code, const char* msg);  // pt_abi.hip: the text of ptmi_last_error()
+
+constexpr int kUpdBlock = 256;
+constexpr int kRefFloats = 12;   // a ref_nodes row (include/ptmi.h)
+constexpr int kNodeFloats = 20;  // a nodes row
+
+// One list of edits as a kernel argument, with what its type fixes.
+struct UpdList {
+  const int32_t* prim;
+  const int32_t* leaf;
+  const float* row;
+  const float* build;
+  float* prims;      // the type's primitive array
+  int32_t count;
+  int32_t num_prims;
+  int32_t type;      // the type code of a leaf: 0 sphere, 1 triangle, 2 quad
+  int32_t row_floats, build_floats;
+};
+
+__device__ __forceinline__ void upd_store_box(float* ref, const UpdBox& b) {
+  for (int k = 0; k < 3; ++k) {
+    ref[k] = b.mn[k];
+    ref[4 + k] = b.mx[k];
+  }
+}
+
+__device__ __forceinline__ UpdBox upd_load_box(const float* ref) {
+  UpdBox b;
+  for (int k = 0; k < 3; ++k) {
+    b.mn[k] = ref[k];
+    b.mx[k] = ref[4 + k];
+  }
+  return b;
+}
+
+__global__ __launch_bounds__(kUpdBlock) void upd_leaves(UpdList s, UpdList q, UpdList t, float* __restrict__ ref_nodes,
+                                                        int32_t num_bvh_nodes) {
+  int32_t i = (int32_t)(blockIdx.x * (uint32_t)kUpdBlock + threadIdx.x);
+  UpdList e = s;
+  if (i >= s.count) {
+    i -= s.count;
+    e = q;
+    if (i >= q.count) {
+      i -= q.count;
+      e = t;
+      if (i >= t.count) return;
+    }
+  }
+  const int32_t p = e.prim[i], leaf = e.leaf[i];
+  if (p < 0 || p >= e.num_prims || leaf < 0 || leaf >= num_bvh_nodes) return;
+  float* ref = ref_nodes + (size_t)leaf * kRefFloats;
+  // leaf code 0x80000000 | type << 28 | class << 25 | index: this primitive's leaf?
+  const uint32_t code = __float_as_uint(ref[9]);
+  if ((code >> 28) != (8u | (uint32_t)e.type) || (code & 0x1ffffffu) != (uint32_t)p) return;
+  const float* row = e.row + (size_t)i * e.row_floats;
+  float* dst = e.prims + (size_t)p * e.row_floats;
+  for (int k = 0; k < e.row_floats; ++k) dst[k] = row[k];
+  const float* rec = e.build + (size_t)i * e.build_floats;
+  float b9[9];
+  for (int k = 0; k < 9; ++k) b9[k] = (k < e.build_floats) ? rec[k] : 0.0f;
+  const UpdBox box = e.type == 0 ? upd_sphere_box(b9) : e.type == 2 ? upd_quad_box(b9) : upd_tri_box(b9);
+  upd_store_box(ref, box);
+}
+
+// Internal node i: the union of its children's boxes into ref_nodes[i], their
+// boxes and centres into row slot[i] of nodes.
+__device__ __forceinline__ void upd_refit_node(int32_t i, const int32_t* __restrict__ slot, float* ref_nodes,
+                                               float* __restrict__ nodes, int32_t num_bvh_nodes, int32_t n_inner) {
+  if (i < 0 || i >= num_bvh_nodes) return;
+  float* ref = ref_nodes + (size_t)i * kRefFloats;
+  const int32_t l = __float_as_int(ref[3]), r = __float_as_int(ref[7]), sl = slot[i];
+  if (l < 0 || l >= num_bvh_nodes || r < 0 || r >= num_bvh_nodes || sl < 0 || sl >= n_inner) return;
+  const UpdBox bl = upd_load_box(ref_nodes + (size_t)l * kRefFloats);
+  const UpdBox br = upd_load_box(ref_nodes + (size_t)r * kRefFloats);
+  upd_store_box(ref, upd_union(bl, br));
+  float4* row = (float4*)(nodes + (size_t)sl * kNodeFloats);  // 80-B rows of a 16-B aligned array
+  row[0] = make_float4(bl.mn[0], br.mn[0], bl.mn[1], br.mn[1]);
+  row[1] = make_float4(bl.mn[2], br.mn[2], bl.mx[0], br.mx[0]);
+  row[2] = make_float4(bl.mx[1], br.mx[1], bl.mx[2], br.mx[2]);
+  ((float2*)row)[7] = make_float2(upd_centre(bl, 2), upd_centre(br, 2));  // f32 14, 15; 12 and 13 are the refs
+  row[4] = make_float4(upd_centre(bl, 0), upd_centre(br, 0), upd_centre(bl, 1), upd_centre(br, 1));
+}
+
+__global__ __launch_bounds__(kUpdBlock) void upd_refit(const int32_t* __restrict__ order, int32_t begin, int32_t end,
+                                                       const int32_t* __restrict__ slot, float* ref_nodes,
+                                                       float* __restrict__ nodes, int32_t num_bvh_nodes,
+                                                       int32_t n_inner) {
+  const int32_t j = begin + (int32_t)(blockIdx.x * (uint32_t)kUpdBlock + threadIdx.x);
+  if (j >= end) return;
+  upd_refit_node(order[j], slot, ref_nodes, nodes, num_bvh_nodes, n_inner);
+}
+
+// The single-workgroup form (PTMI_UPDATE_ONE_GROUP): one block walks the levels
+// itself. All its waves share one CU and its vector L1, so a level's stores are
+// visible to the next level's loads behind __syncthreads(); the level ends are a
+// kernel argument, so every wave runs the same number of barriers.
+constexpr int kUpdOneBlock = 1024;
+struct UpdLevels {
+  int32_t n;
+  int32_t end[PTMI_UPDATE_ONE_GROUP_MAX_LEVELS];
+};
+
+__global__ __launch_bounds__(kUpdOneBlock) void upd_refit_one(const int32_t* __restrict__ order, UpdLevels lv,
+                                                              const int32_t* __restrict__ slot, float* ref_nodes,
+                                                              float* __restrict__ nodes, int32_t num_bvh_nodes,
+                                                              int32_t n_inner) {
+  int32_t begin = 0;
+  for (int32_t j = 0; j < lv.n; ++j) {
+    const int32_t end = lv.end[j];
+    for (int32_t k = begin + (int32_t)threadIdx.x; k < end; k += kUpdOneBlock)
+      upd_refit_node(order[k], slot, ref_nodes, nodes, num_bvh_nodes, n_inner);
+    begin = end;
+    __syncthreads();
+  }
+}
+
+__global__ void upd_root(const float* __restrict__ ref_nodes, float* __restrict__ root_box) {
+  const int k = (int)threadIdx.x;
+  if (k < 6) root_box[k] = ref_nodes[k < 3 ? k : k + 1];
+}
+
+static bool upd_fill(UpdList& d, const ptmi_update_list* s, const float* prims, int32_t num_prims, int32_t type,
+                     int32_t row_floats, int32_t build_floats) {
+  d.prim = s ? s->prim : nullptr;
+  d.leaf = s ? s->leaf : nullptr;
+  d.row = s ? s->row : nullptr;
+  d.build = s ? s->build : nullptr;
+  d.prims = const_cast<float*>(prims);
+  d.count = s ? s->count : 0;
+  d.num_prims = num_prims;
+  d.type = type;
+  d.row_floats = row_floats;
+  d.build_floats = build_floats;
+  return d.count >= 0 && d.count <= num_prims;
+}
+
+static bool upd_bad_ptr(const void* p) { return !p || ((uintptr_t)p & 3u); }
+
+}  // namespace ptmi
+
+using namespace ptmi;
+
+extern "C" {
+
+int ptmi_update_primitives(const ptmi_scene_view* scene, const ptmi_update_list* spheres,
+                           const ptmi_update_list* quads, const ptmi_update_list* tris,
+                           const ptmi_update_topology* topo, float* root_box, void* stream) {
+  if (!scene) return set_last_error(PTMI_EINVAL, "update: scene is NULL");
+  if (scene->n_inner < 0 || scene->num_bvh_nodes < 0 || scene->num_spheres < 0 || scene->num_quads < 0 ||
+      scene->num_triangles < 0 || (scene->n_inner > 0 && scene->num_bvh_nodes != 2 * scene->n_inner + 1))
+    return set_last_error(PTMI_EINVAL, "update: bad scene counts (num_bvh_nodes must be 2 * n_inner + 1)");
+  UpdList s, q, t;
+  if (!upd_fill(s, spheres, scene->spheres, scene->num_spheres, 0, 4, 4))
+    return set_last_error(PTMI_EINVAL, "update: sphere count negative or above num_spheres");
+  if (!upd_fill(q, quads, scene->quads, scene->num_quads, 2, 16, 9))
+    return set_last_error(PTMI_EINVAL, "update: quad count negative or above num_quads");
+  if (!upd_fill(t, tris, scene->tris, scene->num_triangles, 1, 12, 9))
+    return set_last_error(PTMI_EINVAL, "update: triangle count negative or above num_triangles");
+  const struct {
+    const UpdList& l;
+    const char* msg;
+  } lists[3] = {{s, "update: a sphere list pointer is NULL/misaligned"},
+                {q, "update: a quad list pointer is NULL/misaligned"},
+                {t, "update: a triangle list pointer is NULL/misaligned"}};
+  for (const auto& e : lists)
+    if (e.l.count > 0 && (upd_bad_ptr(e.l.prim) || upd_bad_ptr(e.l.leaf) || upd_bad_ptr(e.l.row) ||
+                          upd_bad_ptr(e.l.build) || upd_bad_ptr(e.l.prims)))
+      return set_last_error(PTMI_EINVAL, e.msg);
+  const int32_t n_inner = scene->n_inner;
+  const int64_t n_edits = (int64_t)s.count + q.count + t.count;
+  if ((n_inner > 0 || n_edits > 0) && upd_bad_ptr(scene->ref_nodes))
+    return set_last_error(PTMI_EINVAL, "update: ref_nodes NULL/misaligned");
+  if (n_inner > 0) {
+    if (!scene->nodes || ((uintptr_t)scene->nodes & 15u))
+      return set_last_error(PTMI_EINVAL, "update: nodes NULL/misaligned");
+    if (!topo) return set_last_error(PTMI_EINVAL, "update: topo is NULL");
+    if (upd_bad_ptr(topo->order)) return set_last_error(PTMI_EINVAL, "update: order NULL/misaligned");
+    if (upd_bad_ptr(topo->slot)) return set_last_error(PTMI_EINVAL, "update: slot NULL/misaligned");
+    if (!root_box || ((uintptr_t)root_box & 3u)) return set_last_error(PTMI_EINVAL, "update: root_box NULL/misaligned");
+    if (!topo->level_end || topo->n_levels < 1)
+      return set_last_error(PTMI_EINVAL, "update: level_end is NULL or n_levels < 1");
+    int32_t prev = 0;
+    for (int32_t j = 0; j < topo->n_levels; ++j) {
+      if (topo->level_end[j] <= prev || topo->level_end[j] > n_inner)
+        return set_last_error(PTMI_EINVAL, "update: level ends must ascend strictly to n_inner");
+      prev = topo->level_end[j];
+    }
+    if (prev != n_inner) return set_last_error(PTMI_EINVAL, "update: level ends must ascend strictly to n_inner");
+    if (topo->flags & ~PTMI_UPDATE_ONE_GROUP) return set_last_error(PTMI_EINVAL, "update: unknown flags");
+    if ((topo->flags & PTMI_UPDATE_ONE_GROUP) && topo->n_levels > PTMI_UPDATE_ONE_GROUP_MAX_LEVELS)
+      return set_last_error(PTMI_EINVAL, "update: too many levels for PTMI_UPDATE_ONE_GROUP");
+  }
+  if (scene->num_bvh_nodes == 0) return PTMI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  float* ref_nodes = const_cast<float*>(scene->ref_nodes);
+  if (n_edits > 0)
+    hipLaunchKernelGGL(upd_leaves, dim3((unsigned)((n_edits + kUpdBlock - 1) / kUpdBlock)), dim3(kUpdBlock), 0, st, s, q,
+                       t, ref_nodes, scene->num_bvh_nodes);
+  if (n_inner > 0 && (topo->flags & PTMI_UPDATE_ONE_GROUP)) {
+    UpdLevels lv;
+    lv.n = topo->n_levels;
+    for (int32_t j = 0; j < topo->n_levels; ++j) lv.end[j] = topo->level_end[j];
+    hipLaunchKernelGGL(upd_refit_one, dim3(1), dim3(kUpdOneBlock), 0, st, topo->order, lv, topo->slot, ref_nodes,
+                       const_cast<float*>(scene->nodes), scene->num_bvh_nodes, n_inner);
+  } else if (n_inner > 0) {
+    int32_t begin = 0;
+    for (int32_t j = 0; j < topo->n_levels; ++j) {
+      const int32_t end = topo->level_end[j];
+      hipLaunchKernelGGL(upd_refit, dim3((unsigned)((end - begin + kUpdBlock - 1) / kUpdBlock)), dim3(kUpdBlock), 0, st,
+                         topo->order, begin, end, topo->slot, ref_nodes, const_cast<float*>(scene->nodes),
+                         scene->num_bvh_nodes, n_inner);
+      begin = end;
+    }
+  }
+  if (root_box && ref_nodes) hipLaunchKernelGGL(upd_root, dim3(1), dim3(64), 0, st, ref_nodes, root_box);
+  const hipError_t e = hipGetLastError();
+  if (e == hipSuccess) return PTMI_OK;
+  return set_last_error(PTMI_EHIP, hipGetErrorString(e));
+}
+
+}  // extern "C"

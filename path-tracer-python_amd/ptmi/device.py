@@ -9,13 +9,15 @@ object, so several scenes can coexist in one process.
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import os
 
 import numpy as np
 import torch
 
-from . import _lib, guide, post, temporal, wf_tiles
-from .scene_data import DeviceLayout, SceneArrays, camera_upload, pack_device
+from . import _lib, guide, post, temporal, update, wf_tiles
+from .scene_data import (DeviceLayout, PRIM_QUAD, PRIM_SPHERE, PRIM_TRIANGLE, SceneArrays, camera_upload,
+                         fill_node_boxes, pack_device, shell_hint)
 
 
 def _stream_ptr(stream=None, device=None):
@@ -45,6 +47,9 @@ class DeviceScene:
             raise _lib.PtmiError(f'scene packed with {layout.nodes.shape[1] * 4}-B nodes, '
                                  f'libptmi expects {node_bytes}')
         self.layout = layout
+        # the reference-layout arrays the scene was packed from: update_primitives keeps them equal to the device
+        self.arrays = scene if isinstance(scene, SceneArrays) else None
+        self._upd = None  # update_primitives' topology, index maps and root box, made by its first call
         dev = torch.device(device if device is not None else 'cuda')
         if dev.type != 'cuda':
             raise _lib.PtmiError(f'DeviceScene needs a cuda device, got {dev}')
@@ -100,6 +105,161 @@ class DeviceScene:
     @classmethod
     def from_arrays(cls, sa: SceneArrays, device=None):
         return cls(sa, device)
+
+    # ------------------------------------------------ scene updates (ptmi.update)
+    def _update_state(self):
+        """Topology arrays, index maps and the mirror of update_primitives, made once."""
+        if self._upd is not None:
+            return self._upd
+        sa, lay = self.arrays, self.layout
+        if sa is None or len(lay.prim_perm) != 3:
+            raise _lib.PtmiError('update_primitives needs a DeviceScene made from SceneArrays (it maps reference '
+                                 'primitive indices and keeps the arrays equal to the device)')
+        if self.t_ref_nodes is None:
+            raise _lib.PtmiError('update_primitives needs the scene\'s ref_nodes')
+        # the mirror: the geometry and the boxes are copied, so the caller's arrays stay as they were
+        b = dict(sa.bvh, bvh_bbox_min=sa.bvh['bvh_bbox_min'].copy(), bvh_bbox_max=sa.bvh['bvh_bbox_max'].copy())
+        self.arrays = sa = dataclasses.replace(sa, sphere_data=sa.sphere_data.copy(), bvh=b,
+                                               quads={k: v.copy() for k, v in sa.quads.items()},
+                                               tris={k: v.copy() for k, v in sa.tris.items()})
+        for name in ('nodes', 'spheres', 'quads', 'tris', 'ref_nodes', 'root_min', 'root_max'):
+            setattr(lay, name, np.array(getattr(lay, name)))  # the layout is refreshed in place: its own copy
+        order, level_end, slot = update.topology(b)
+        ptype, pidx = b['bvh_prim_type'], b['bvh_prim_idx']
+        leaves = np.nonzero(pidx >= 0)[0]
+        leaf_of, dev_of = [], []
+        for t, n in enumerate((sa.num_spheres, sa.num_triangles, sa.num_quads)):  # by type code
+            sel = leaves[ptype[leaves] == t]
+            lo = np.full(n, -1, np.int64)
+            lo[pidx[sel]] = sel
+            inv = np.empty(n, np.int64)
+            inv[lay.prim_perm[t]] = np.arange(n)
+            leaf_of.append(lo)
+            dev_of.append(inv)
+        inner = np.nonzero(pidx < 0)[0]
+        dev = self.device
+        self._upd = {
+            'order': torch.from_numpy(order).to(dev) if order.size else None,
+            'slot': torch.from_numpy(slot).to(dev) if slot.size else None,
+            'level_end': (C.c_int32 * max(1, level_end.size))(*level_end.tolist()), 'n_levels': int(level_end.size),
+            'leaf_of': leaf_of, 'dev_of': dev_of, 'root': torch.zeros(6, dtype=torch.float32, device=dev),
+            'inner': inner, 'rows': slot[inner].astype(np.int64),
+            'left': b['bvh_left_child'][inner], 'right': b['bvh_right_child'][inner], 'slot_np': slot}
+        return self._upd
+
+    def update_call(self, lists, stream=None, flags=None):
+        """ptmi_update_primitives on this scene: ``lists`` maps a primitive type
+        code to (prim ptr, leaf ptr, row ptr, build ptr, count) of edits already
+        on the device. ``flags``: PTMI_UPDATE_* (0: one launch per level;
+        update.ONE_GROUP: the single-workgroup refit), by default
+        update.refit_flags' choice for the tree's size. Asynchronous; the host
+        mirror and the view are not refreshed (update_primitives does both)."""
+        st = self._update_state()
+        if flags is None:
+            flags = update.refit_flags(self.layout.n_inner, st['n_levels'])
+        arg = []
+        for t in (PRIM_SPHERE, PRIM_QUAD, PRIM_TRIANGLE):
+            e = lists.get(t)
+            arg.append(C.byref(update.UpdateList(*e)) if e is not None and e[4] else None)
+        topo = update.UpdateTopology(st['order'].data_ptr() if st['order'] is not None else None,
+                                     st['slot'].data_ptr() if st['slot'] is not None else None,
+                                     st['level_end'], st['n_levels'], int(flags))
+        with torch.cuda.device(self.device):
+            _lib.check(update.load().ptmi_update_primitives(self.view, arg[0], arg[1], arg[2], C.byref(topo),
+                                                            st['root'].data_ptr(), _stream_ptr(stream, self.device)),
+                       'ptmi_update_primitives')
+
+    def update_primitives(self, spheres=None, quads=None, triangles=None, stream=None, flags=None):
+        """Move primitives and refit the BVH on the device (include/ptmi_update.h,
+        DESIGN.md §17). Each argument is ``(reference primitive indices, rows,
+        build records)``: numpy arrays of n indices, (n, 4 / 16 / 12) f32 device
+        rows as include/ptmi.h lays them out and (n, 4 / 9 / 9) f32 builder-form
+        records ({c, r}; {Q, u, v}; {v0, v1, v2}). Indices out of range or
+        repeated, and rows that contradict their build record, are a ValueError
+        before anything is uploaded. No render of this scene may be in flight
+        on another stream. On return the device is updated, ``arrays`` (the
+        reference-layout mirror) and ``layout`` equal what the device holds,
+        the view's root box is refreshed and its shell hint re-evaluated
+        (scene_data.find_shell on the mirror; 0 if the claim no longer holds).
+        Topology, materials and counts do not change: for anything else build a
+        new DeviceScene. ``flags`` as for update_call (same bits either way)."""
+        st = self._update_state()
+        sa, lay = self.arrays, self.layout
+        edits, ints, floats, lists, ni, nf = {}, [], [], {}, 0, 0
+        for t, arg, name in ((PRIM_SPHERE, spheres, 'spheres'), (PRIM_QUAD, quads, 'quads'),
+                             (PRIM_TRIANGLE, triangles, 'triangles')):
+            if arg is None:
+                continue
+            idx, rows, build = arg
+            idx = np.asarray(idx)
+            n, count = int(idx.size), int(st['leaf_of'][t].shape[0])
+            if idx.ndim != 1 or (n and not np.issubdtype(idx.dtype, np.integer)):
+                raise ValueError(f'{name}: indices must be a 1-D integer array')
+            idx = idx.astype(np.int64)
+            if n and (idx.min() < 0 or idx.max() >= count):
+                raise ValueError(f'{name}: an index is outside [0, {count})')
+            if np.unique(idx).size != n:
+                raise ValueError(f'{name}: an index is repeated')
+            rows, build = np.ascontiguousarray(rows, np.float32), np.ascontiguousarray(build, np.float32)
+            if rows.size != n * update.ROW_FLOATS[t] or build.size != n * update.BUILD_FLOATS[t]:
+                raise ValueError(f'{name}: rows must be (n, {update.ROW_FLOATS[t]}) and build records '
+                                 f'(n, {update.BUILD_FLOATS[t]}) f32')
+            rows, build = rows.reshape(n, update.ROW_FLOATS[t]), build.reshape(n, update.BUILD_FLOATS[t])
+            if not (np.isfinite(rows).all() and np.isfinite(build).all()):
+                raise ValueError(f'{name}: rows and build records must be finite')
+            same = {PRIM_SPHERE: (rows, build), PRIM_QUAD: (rows[:, 4:13], build),
+                    PRIM_TRIANGLE: (rows[:, 0:3], build[:, 0:3])}[t]
+            if same[0].tobytes() != same[1].tobytes():
+                raise ValueError(f'{name}: a row and its build record name different points')
+            if n == 0:
+                continue
+            prim, leaf = st['dev_of'][t][idx], st['leaf_of'][t][idx]
+            edits[t] = (idx, rows, build, prim)
+            ints += [prim.astype(np.int32), leaf.astype(np.int32)]
+            floats += [rows.reshape(-1), build.reshape(-1)]
+            lists[t] = (ni, ni + n, nf, nf + rows.size, n)  # element offsets, made pointers below
+            ni, nf = ni + 2 * n, nf + rows.size + build.size
+        if ints:
+            ti = torch.from_numpy(np.concatenate(ints)).to(self.device)
+            tf = torch.from_numpy(np.concatenate(floats)).to(self.device)
+            pi, pf = ti.data_ptr(), tf.data_ptr()
+            lists = {t: (pi + 4 * a, pi + 4 * b, pf + 4 * c, pf + 4 * d, n) for t, (a, b, c, d, n) in lists.items()}
+        self.update_call(lists, stream, flags)
+        (stream if stream is not None else torch.cuda.current_stream(self.device)).synchronize()
+        # the mirror: the boxes from the device, the edited primitives from the arguments
+        nb = sa.num_bvh_nodes
+        if nb:
+            rn = self.t_ref_nodes.cpu().numpy().reshape(-1, 12)
+            sa.bvh['bvh_bbox_min'][:] = rn[:nb, 0:3]
+            sa.bvh['bvh_bbox_max'][:] = rn[:nb, 4:7]
+        for t, (idx, rows, build, prim) in edits.items():
+            if t == PRIM_SPHERE:
+                sa.sphere_data[idx] = rows
+                lay.spheres[prim] = rows
+            elif t == PRIM_QUAD:
+                for key, a, b in (('quad_normal', 0, 3), ('quad_Q', 4, 7), ('quad_u', 7, 10), ('quad_v', 10, 13),
+                                  ('quad_w', 13, 16)):
+                    sa.quads[key][idx] = rows[:, a:b]
+                sa.quads['quad_D'][idx] = rows[:, 3]
+                lay.quads[prim] = rows
+            else:
+                for key, src, a in (('triangle_v0', build, 0), ('triangle_v1', build, 3), ('triangle_v2', build, 6),
+                                    ('triangle_edge1', rows, 3), ('triangle_edge2', rows, 6),
+                                    ('triangle_normal', rows, 9)):
+                    sa.tris[key][idx] = src[:, a:a + 3]
+                lay.tris[prim] = rows
+        if nb:
+            lay.ref_nodes[:] = rn[:nb]
+            if st['inner'].size:
+                fill_node_boxes(lay.nodes, st['rows'], sa.bvh['bvh_bbox_min'], sa.bvh['bvh_bbox_max'], st['left'],
+                                st['right'])
+            lay.root_min[:], lay.root_max[:] = rn[0, 0:3], rn[0, 4:7]
+            lay.shell = shell_hint(sa, st['slot_np'], lay.max_leaf_depth, lay.nodes.shape[1] * 4)
+            for k in range(3):
+                self.view.root_min[k] = float(lay.root_min[k])
+                self.view.root_max[k] = float(lay.root_max[k])
+            self.view.shell = int(lay.shell)
+        _lib.check(_lib.load().ptmi_scene_check(self.view), 'ptmi_scene_check')
 
 
 def make_frame(cam, bg, max_depth, seed, width, height, window=None, band=(1, 1, 0), traversal='stack'):

@@ -140,6 +140,17 @@ class InteractiveViewer(MI355XRenderer):
         self.is_rendering_active = True
         print(f"\n{'─' * 60}\nCamera rotated - restarting render from sample 0\n{'─' * 60}")
 
+    def update_primitives(self, spheres=None, quads=None, triangles=None):
+        """MI355XRenderer.update_primitives; the temporal history is dropped
+        with the image: there are no motion vectors, so a surface point of the
+        old scene says nothing about the new one."""
+        super().update_primitives(spheres, quads, triangles)
+        self._history_cam = self._history_guides = None
+        self._history_kept = False
+        self.history_fraction = None
+        self.render_start_time = time.time()
+        self.is_rendering_active = True
+
     # ------------------------------------------------------- mouse handlers
     def on_mouse_down(self, event):
         self.mouse_down = True

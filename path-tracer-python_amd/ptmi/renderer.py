@@ -43,6 +43,11 @@ Temporal reprojection (no counterpart in the reference):
 the stats of a stats render to the camera uploaded since, by the guides of both
 cameras; InteractiveViewer(temporal=True) does so on every
 camera move. Derived state: not checkpointed.
+
+Scene updates (no counterpart in the reference): ``update_primitives`` moves
+spheres, quads and triangles of the resident scene and refits the BVH on the
+device instead of building a new renderer; ``primitives`` lists
+the objects by the indices it takes. The image starts over.
 """
 from __future__ import annotations
 
@@ -98,14 +103,19 @@ class MI355XRenderer:
         self.guide_trace_seconds = None
         # reproject_history(): the (accum, stats) pair it writes into next, swapped with the live pair on each call
         self._history_spare = None
+        # update_primitives(): bumped on every scene update; part of the guides' cache key
+        self.scene_revision = 0
         # launches per progress report: one launch renders many samples (path regeneration)
         self.samples_per_launch = int(samples_per_launch)
         device.require_gpu()
         # renderer.py:78-80: Perlin tables from a perlin() made after the scene
         perlin = core.perlin()
         t0 = time.time()
-        (geom, mats, spheres, qgeom, qmats, quads, tgeom, tmats, tris, _reg,
+        (geom, mats, spheres, qgeom, qmats, quads, tgeom, tmats, tris, img_reg,
          img_list) = scene_compiler.compile_scene(world)
+        # the primitive objects in compile order and the image registry: update_primitives checks replacements by them
+        self._prims = {'spheres': spheres, 'quads': quads, 'triangles': tris}
+        self._img_reg = img_reg
         self.timing['scene_compile'] = time.time() - t0
         t0 = time.time()
         bvh = bvh_mod.compile_bvh(world, spheres, quads, tris)
@@ -317,7 +327,7 @@ class MI355XRenderer:
     def _guide_key(self):
         f = self.frame
         cam = tuple(float(v) for k in ('center', 'pixel00', 'delta_u', 'delta_v') for v in getattr(f.cam, k))
-        return cam + (int(f.width), int(f.height), int(f.traversal))
+        return cam + (int(f.width), int(f.height), int(f.traversal), self.scene_revision)
 
     def guides(self):
         """First-hit guide buffers of the current camera (Integrator.trace_guides,
@@ -341,6 +351,72 @@ class MI355XRenderer:
         g = self.guides().cpu().numpy()
         return {'normal': g[..., 0:3].copy(), 'depth': g[..., 3].copy(), 'albedo': g[..., 4:7].copy(),
                 'hit': g[..., 7] != 0}
+
+    # ----------------------------------------------------------- scene updates
+    @property
+    def primitives(self):
+        """The scene's primitive objects in compile order, {'spheres': [...],
+        'quads': [...], 'triangles': [...]}: the indices update_primitives takes."""
+        return self._prims
+
+    _REBUILD = 'for any other edit build a new MI355XRenderer from the edited world'
+
+    def update_primitives(self, spheres=None, quads=None, triangles=None):
+        """Move primitives of the resident scene and refit its BVH on the device
+        (DeviceScene.update_primitives, include/ptmi_update.h).
+        Each argument maps a reference primitive index (the primitive's place
+        in ``compile_scene``'s sphere, quad or triangle list) to the new
+        ``Sphere`` / ``quad`` / ``triangle`` object. Only geometry changes:
+        the object must be of the list's kind and compile to the material
+        record the primitive has; counts, order, media and the BVH topology
+        stay (a refit tree traverses slower the further objects scatter).
+        Anything else is a ValueError: the rebuild path is a new renderer.
+
+        The image starts over: the accumulator is cleared, the adaptive state
+        is reset as for a new adaptive render, ``denoised`` and the
+        reprojection spare pair are dropped, and the guides are retraced on
+        their next use. ``arrays`` is afterwards what the device holds, with
+        the geometry arrays of a full compile of the edited world."""
+        kinds = {'spheres': ('Sphere', 'sphere_mats', lambda o: o.material, lambda o: o.center.at(0.0)),
+                 'quads': ('quad', 'quad_mats', lambda o: o.mat, lambda o: o.Q),
+                 'triangles': ('triangle', 'tri_mats', lambda o: o.mat, lambda o: o.v0)}
+        given = {'spheres': spheres or {}, 'quads': quads or {}, 'triangles': triangles or {}}
+        for name, new in given.items():
+            kind, mats_name, get_mat, get_ref = kinds[name]
+            mats, have = getattr(self.arrays, mats_name), self._prims[name]
+            for i, obj in new.items():
+                if not isinstance(i, (int, np.integer)) or not 0 <= i < len(have):
+                    raise ValueError(f'{name}: no primitive {i!r} (the scene has {len(have)}); {self._REBUILD}')
+                if type(obj).__name__ != kind:
+                    raise ValueError(f'{name}[{i}]: a {type(obj).__name__} cannot replace a {kind}; {self._REBUILD}')
+                row = scene_compiler._material_row(get_mat(obj), get_ref(obj), self._img_reg)
+                for k, v in row.items():
+                    if np.asarray(v, mats[k].dtype).tobytes() != mats[k][i].tobytes():
+                        raise ValueError(f'{name}[{i}]: the new object changes {k}; materials are fixed, '
+                                         f'{self._REBUILD}')
+        order = {name: sorted(new) for name, new in given.items()}
+        records = scene_compiler.update_records(*([given[name][i] for i in order[name]]
+                                                  for name in ('spheres', 'quads', 'triangles')))
+        args = [(np.asarray(order[name], np.int64), rows, build) if order[name] else None
+                for name, (rows, build) in zip(('spheres', 'quads', 'triangles'), records)]
+        import torch
+        torch.cuda.synchronize(self.dscene.device)  # no render of the scene in flight on any stream (overlapped traces)
+        self.dscene.update_primitives(*args)
+        for name, new in given.items():
+            for i, obj in new.items():
+                self._prims[name][i] = obj
+        self.arrays = self.dscene.arrays
+        self.scene_revision += 1
+        self.clear_accumulation_buffer()
+        self.current_sample = 0
+        self.sample_times = []
+        self.adaptive_passes = []
+        if self.stats is not None:
+            self._adaptive_reset()
+        self.denoised = self.denoised_var = self.denoise_seconds = None
+        self._history_spare = None
+        self._guides = None
+        self.integrator.reset_counters()
 
     def reproject_history(self, prev_camera, prev_guides, again=False, **params):
         """Carry ``accum`` and ``stats`` of a stats render from ``prev_camera``

@@ -280,6 +280,21 @@ def compile_scene(world):
             img_reg, img_list)
 
 
+def update_records(spheres=(), quads=(), triangles=()):
+    """Device rows and builder-form records of primitive objects, for a scene
+    update (DeviceScene.update_primitives): per type (rows, build), each from
+    the arithmetic compile_scene and compile_bvh apply to that primitive
+    (compile_geometry / compile_quad_geometry / compile_triangle_geometry and
+    bvh.primitive_inputs), so an updated scene's geometry arrays equal those of
+    a full compile of the edited world."""
+    from . import bvh as bvh_mod, scene_data
+    spheres, quads, triangles = list(spheres), list(quads), list(triangles)
+    sp, qd, tr = bvh_mod.primitive_inputs(spheres, quads, triangles)
+    return ((compile_geometry(spheres)['sphere_data'], sp),
+            (scene_data.pack_quads(compile_quad_geometry(quads)), qd),
+            (scene_data.pack_tris(compile_triangle_geometry(triangles)), tr))
+
+
 def image_u8(tex):
     """RGB8 payload of an image texture: ptmi.core stores it; the reference's
     rtw_image keeps fdata = u8/255 (f32), inverted exactly by rounding."""

@@ -392,6 +392,54 @@ def find_shell(sa: SceneArrays, max_leaf_depth: int):
     return best
 
 
+def pack_quads(q):
+    """Device rows (include/ptmi.h: 16 f32) of reference-layout quad arrays (QUAD_KEYS), in their order."""
+    quads = np.zeros((q['quad_Q'].shape[0], 16), np.float32)
+    quads[:, 0:3] = q['quad_normal']
+    quads[:, 3] = q['quad_D']
+    quads[:, 4:7] = q['quad_Q']
+    quads[:, 7:10] = q['quad_u']
+    quads[:, 10:13] = q['quad_v']
+    quads[:, 13:16] = q['quad_w']
+    return quads
+
+
+def pack_tris(t):
+    """Device rows (12 f32) of reference-layout triangle arrays (TRI_KEYS), in their order."""
+    tris = np.zeros((t['triangle_v0'].shape[0], 12), np.float32)
+    tris[:, 0:3] = t['triangle_v0']
+    tris[:, 3:6] = t['triangle_edge1']
+    tris[:, 6:9] = t['triangle_edge2']
+    tris[:, 9:12] = t['triangle_normal']
+    return tris
+
+
+def fill_node_boxes(nodes, rows, bmin, bmax, l, r):
+    """The box part of node rows ``rows`` (include/ptmi.h): the boxes of the
+    children ``l`` and ``r`` interleaved per component, and their centres. The
+    two refs (f32 12, 13) are not touched."""
+    nodes[rows, 0:12:2] = np.concatenate([bmin[l], bmax[l]], axis=1)
+    nodes[rows, 1:12:2] = np.concatenate([bmin[r], bmax[r]], axis=1)
+    # box centres (min + max) * 0.5 in f32 — the same rounding as the
+    # kernels' (kernels.py:707-710), so precomputing them changes nothing
+    cl = (bmin[l] + bmax[l]) * np.float32(0.5)
+    cr = (bmin[r] + bmax[r]) * np.float32(0.5)
+    nodes[rows, 14], nodes[rows, 15] = cl[:, 2], cr[:, 2]
+    nodes[rows, 16], nodes[rows, 17] = cl[:, 0], cr[:, 0]
+    nodes[rows, 18], nodes[rows, 19] = cl[:, 1], cr[:, 1]
+
+
+def shell_hint(sa: SceneArrays, slot, max_leaf_depth: int, node_bytes: int = NODE_BYTES) -> int:
+    """The ``shell`` value of include/ptmi.h for find_shell's leaf: 1 + the byte
+    offset of the node holding the shell's leaf as a child + the child index;
+    0 without a shell. ``slot``: node_slots' rows."""
+    leaf = find_shell(sa, max_leaf_depth)
+    if leaf <= 0:
+        return 0
+    par = int(sa.bvh['bvh_parent'][leaf])
+    return 1 + int(slot[par]) * node_bytes + (0 if int(sa.bvh['bvh_left_child'][par]) == leaf else 1)
+
+
 def pack_device(sa: SceneArrays, node_bytes: int = NODE_BYTES, leaf_order: bool = True) -> DeviceLayout:
     """Reference-layout arrays -> include/ptmi.h device layout. ``node_bytes``
     is the library's node stride (ptmi_node_bytes(): 80, one child record
@@ -445,20 +493,12 @@ def pack_device(sa: SceneArrays, node_bytes: int = NODE_BYTES, leaf_order: bool 
         raise ValueError(f'{nrows} BVH node rows: byte offsets exceed int32')
     refs = np.where(is_leaf, codes, (cidx * node_bytes).astype(np.int32)).astype(np.int32)
     nodes = np.zeros((nrows, node_bytes // 4), np.float32)
-    if internal.size:  # children interleaved per component (include/ptmi.h)
+    if internal.size:
         l, r = left[internal], right[internal]
         rows = cidx[internal]
-        nodes[rows, 0:12:2] = np.concatenate([bmin[l], bmax[l]], axis=1)
-        nodes[rows, 1:12:2] = np.concatenate([bmin[r], bmax[r]], axis=1)
+        fill_node_boxes(nodes, rows, bmin, bmax, l, r)
         nodes[rows, 12] = refs[l].view(np.float32)
         nodes[rows, 13] = refs[r].view(np.float32)
-        # box centres (min + max) * 0.5 in f32 — the same rounding as the
-        # kernels' (kernels.py:707-710), so precomputing them changes nothing
-        cl = (bmin[l] + bmax[l]) * np.float32(0.5)
-        cr = (bmin[r] + bmax[r]) * np.float32(0.5)
-        nodes[rows, 14], nodes[rows, 15] = cl[:, 2], cr[:, 2]
-        nodes[rows, 16], nodes[rows, 17] = cl[:, 0], cr[:, 0]
-        nodes[rows, 18], nodes[rows, 19] = cl[:, 1], cr[:, 1]
     ref_nodes = ref_layout_nodes(b, np.where(is_leaf, codes, 0).astype(np.int32))
     if n:
         root_ref = int(refs[0])
@@ -466,27 +506,9 @@ def pack_device(sa: SceneArrays, node_bytes: int = NODE_BYTES, leaf_order: bool 
         max_leaf_depth = int(leaf_depths(b).max())
     else:
         root_ref, root_min, root_max, max_leaf_depth = 0, np.zeros(3, np.float32), np.zeros(3, np.float32), 0
-    # shell hint: 1 + byte offset of the node holding the shell's leaf as a child + the child index
-    shell, leaf = 0, find_shell(sa, max_leaf_depth)
-    if leaf > 0:
-        par = int(b['bvh_parent'][leaf])
-        shell = 1 + int(cidx[par]) * node_bytes + (0 if int(left[par]) == leaf else 1)
+    shell = shell_hint(sa, cidx, max_leaf_depth, node_bytes)
     spheres =np.ascontiguousarray(np.asarray(sa.sphere_data, np.float32).reshape(ns, 4)[ps])
-    q = sa.quads
-    quads = np.zeros((nq, 16), np.float32)
-    quads[:, 0:3] = q['quad_normal']
-    quads[:, 3] = q['quad_D']
-    quads[:, 4:7] = q['quad_Q']
-    quads[:, 7:10] = q['quad_u']
-    quads[:, 10:13] = q['quad_v']
-    quads[:, 13:16] = q['quad_w']
-    t = sa.tris
-    tris = np.zeros((nt, 12), np.float32)
-    tris[:, 0:3] = t['triangle_v0']
-    tris[:, 3:6] = t['triangle_edge1']
-    tris[:, 6:9] = t['triangle_edge2']
-    tris[:, 9:12] = t['triangle_normal']
-    quads, tris = quads[pq], tris[pt]
+    quads, tris = pack_quads(sa.quads)[pq], pack_tris(sa.tris)[pt]
     if len(sa.images) > MAX_IMAGES:
         raise ValueError(f'at most {MAX_IMAGES} image textures')
     texels, offs, ws, hs, off = [], [], [], [], 0
