@@ -103,8 +103,8 @@ typedef struct ptmi_dn_guided_params {
     int32_t flags;             /* bit 0: PTMI_DN_DEMODULATE; other bits must be 0 */
 } ptmi_dn_guided_params;
 
-/* The guided filter above: dng_load, `iterations` launches of dng_pass,
- * dng_store; the guides are read in place. Asynchronous on `stream`,
+/* The guided filter above: dn_load, `iterations` launches of dn_pass,
+ * dn_store (their GUIDED forms); the guides are read in place. Asynchronous on `stream`,
  * graph-capturable, no allocation, not timed by ptmi_prof_*. PTMI_EINVAL, each
  * with a message and before any HIP call: every case ptmi_denoise rejects
  * (ptmi_post.h; iterations and sigma are the params'); a NULL guides or

@@ -17,6 +17,8 @@
 #include <string>
 
 #include "../../include/ptmi_wf_tiles.h"
+#include "pt_args.hpp"
+#include "pt_image.hpp"
 #include "pt_launch.hpp"
 #include "pt_prof.hpp"
 
@@ -83,8 +85,8 @@ using namespace ptmi;
 
 static thread_local std::string g_err;
 
-static int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-static int fail(int code, const char* fmt, ...) {
+// pt_args.hpp: one slot for the entry points of every translation unit.
+int ptmi::fail(int code, const char* fmt, ...) {
   char buf[512];
   va_list ap;
   va_start(ap, fmt);
@@ -94,18 +96,10 @@ static int fail(int code, const char* fmt, ...) {
   return code;
 }
 
-// The same slot for the entry points of other translation units (pt_denoise.hip).
-namespace ptmi {
-int set_last_error(int code, const char* msg) { return fail(code, "%s", msg); }
-}  // namespace ptmi
-
 static int check_hip(hipError_t e, const char* what) {
   if (e != hipSuccess) return fail(PTMI_EHIP, "%s: %s", what, hipGetErrorString(e));
   return PTMI_OK;
 }
-
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-static bool bad16(const void* p) { return !p || !aligned16(p); }  // NULL or misaligned
 
 static int to_dev_scene(const ptmi_scene_view* s, DevScene& d) {
   if (!s) return fail(PTMI_EINVAL, "scene is NULL");
@@ -135,7 +129,7 @@ static int to_dev_scene(const ptmi_scene_view* s, DevScene& d) {
                 s->max_leaf_depth);
   if (s->num_bvh_nodes != (np > 0 ? 2 * np - 1 : 0))
     return fail(PTMI_EINVAL, "num_bvh_nodes %d for %d primitives (expected 2N-1)", s->num_bvh_nodes, np);
-  if (s->ref_nodes && !aligned16(s->ref_nodes)) return fail(PTMI_EINVAL, "ref_nodes misaligned");
+  if (s->ref_nodes && bad16(s->ref_nodes)) return fail(PTMI_EINVAL, "ref_nodes misaligned");
   // Shell hint (include/ptmi.h): 1 + node byte offset + child index. The
   // kernels read that node, so the offset is checked; what it claims about the
   // scene is the caller's, like a leaf code's class bits.
@@ -217,8 +211,6 @@ static int to_dev_frame(const ptmi_frame* f, DevFrame& d) {
   return PTMI_OK;
 }
 
-static int32_t stack_needed(const ptmi_scene_view* s) { return s->max_leaf_depth + 1; }
-
 // The stackless traversal walks the reference-layout nodes (ref_nodes).
 static int check_traversal(const DevScene& sc, const DevFrame& fr) {
   if (fr.traversal == PTMI_TRAV_STACKLESS && sc.n_nodes > 0 && !sc.ref_nodes)
@@ -227,23 +219,12 @@ static int check_traversal(const DevScene& sc, const DevFrame& fr) {
 }
 
 // ---------------------------------------------------------------- shared checks
-static bool aligned4(const void* p) { return ((uintptr_t)p & 3u) == 0; }
-
-// The prologue of every call that takes a scene.
-static int to_dev(const ptmi_scene_view* scene, const ptmi_frame* frame, DevScene& sc, DevFrame& fr) {
+// The prologue of every call that takes a scene (pt_args.hpp).
+int ptmi::to_dev(const ptmi_scene_view* scene, const ptmi_frame* frame, DevScene& sc, DevFrame& fr) {
   if (int rc = to_dev_scene(scene, sc)) return rc;
   if (int rc = to_dev_frame(frame, fr)) return rc;
   return check_traversal(sc, fr);
 }
-
-// The same prologue for the guide trace of another translation unit (pt_guide.hip).
-namespace ptmi {
-int guide_to_dev(const ptmi_scene_view* scene, const ptmi_frame* frame, DevScene& sc, DevFrame& fr, int32_t& slots) {
-  if (int rc = to_dev(scene, frame, sc, fr)) return rc;
-  slots = stack_needed(scene);
-  return PTMI_OK;
-}
-}  // namespace ptmi
 
 static int check_accum(const float* accum) { return accum ? PTMI_OK : fail(PTMI_EINVAL, "accum is NULL"); }
 static int check_stats(const float* stats) {
@@ -258,12 +239,6 @@ static int check_workspace(const void* ws, size_t bytes, size_t need, bool batch
 
 static bool bad_tile_count(int32_t n_tiles, const DevFrame& fr) {
   return n_tiles < 0 || n_tiles > tile_grid(fr).ntiles;
-}
-
-// One thread per element in grid-stride loops: at most 4096 blocks.
-static dim3 capped_grid(int64_t n) {
-  const int64_t g = (n + kBlock - 1) / kBlock;
-  return dim3((unsigned)(g > 4096 ? 4096 : g));
 }
 
 // ------------------------------- one body per group of entry points (`what` names the public one)
@@ -284,7 +259,7 @@ static int render_ws_any(const char* what, RenderKind kind, const ptmi_scene_vie
     if (int rc = check_stats(stats)) return rc;
   if (listed && bad_tile_count(n_tiles, fr))
     return fail(PTMI_EINVAL, "n_tiles %d outside [0, %lld]", n_tiles, (long long)tile_grid(fr).ntiles);
-  if (listed && n_tiles > 0 && (!tile_list || !aligned4(tile_list)))
+  if (listed && n_tiles > 0 && bad4(tile_list))
     return fail(PTMI_EINVAL, "tile_list NULL/misaligned");
   if (s_begin < 0 || s_count < 0) return fail(PTMI_EINVAL, "bad sample range");
   const int32_t npix = fr.w * fr.n_rows;
@@ -311,7 +286,7 @@ static int mk_trace_any(const char* what, bool listed, const ptmi_scene_view* sc
   if (s_begin < 0 || s_count < 1) return fail(PTMI_EINVAL, "bad sample range");
   if (listed && bad_tile_count(n_tiles, fr))
     return fail(PTMI_EINVAL, "n_tiles %d outside [0, %lld]", n_tiles, (long long)tile_grid(fr).ntiles);
-  if (listed && n_tiles > 0 && (!tile_list || !aligned4(tile_list)))
+  if (listed && n_tiles > 0 && bad4(tile_list))
     return fail(PTMI_EINVAL, "tile_list NULL/misaligned");
   const int32_t npix = fr.w * fr.n_rows;
   if (npix == 0) return PTMI_OK;
@@ -334,7 +309,7 @@ static int mk_resolve_any(const char* what, bool with_stats, const ptmi_frame* f
   if (with_stats)
     if (int rc = check_stats(stats)) return rc;
   if (s_count < 1) return fail(PTMI_EINVAL, "sample_count must be >= 1");
-  if (tile_list && (!aligned4(tile_list) || bad_tile_count(n_tiles, fr)))
+  if (tile_list && (bad4(tile_list) || bad_tile_count(n_tiles, fr)))
     return fail(PTMI_EINVAL, "tile_list misaligned or n_tiles %d outside [0, %lld]", n_tiles,
                 (long long)tile_grid(fr).ntiles);
   const int32_t npix = fr.w * fr.n_rows;
@@ -356,10 +331,11 @@ static int clear_any(bool is_stats, const ptmi_frame* frame, float* buf, void* s
   if (int rc = is_stats ? check_stats(buf) : check_accum(buf)) return rc;
   const int32_t npix = fr.w * fr.n_rows;
   if (npix == 0) return PTMI_OK;
+  const dim3 grid = capped_grid(npix, kBlock);
   if (is_stats)
-    hipLaunchKernelGGL(stats_clear_kernel, capped_grid(npix), dim3(kBlock), 0, (hipStream_t)stream, fr, (float4*)buf);
+    hipLaunchKernelGGL(stats_clear_kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, fr, (float4*)buf);
   else
-    hipLaunchKernelGGL(clear_kernel, capped_grid(npix), dim3(kBlock), 0, (hipStream_t)stream, fr, buf);
+    hipLaunchKernelGGL(clear_kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, fr, buf);
   return check_hip(hipGetLastError(), is_stats ? "stats clear launch" : "clear launch");
 }
 
@@ -372,12 +348,12 @@ static int tonemap_any(bool with_stats, const float* accum, const float* stats, 
   const int64_t n = (int64_t)width * height * 3;
   if (n > 0x7fffffff) return fail(PTMI_ECAPACITY, "image too large");
   const float scale = (float)(1.0 / (double)(spp > 1 ? spp : 1));  // python float -> f32 (NEP 50)
+  const dim3 grid = capped_grid(n, kBlock);
   if (with_stats)
-    hipLaunchKernelGGL(tonemap_stats_kernel, capped_grid(n), dim3(kBlock), 0, (hipStream_t)stream, accum,
-                       (const float4*)stats, out, (int32_t)n);
+    hipLaunchKernelGGL(tonemap_stats_kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, accum, (const float4*)stats,
+                       out, (int32_t)n);
   else
-    hipLaunchKernelGGL(tonemap_kernel, capped_grid(n), dim3(kBlock), 0, (hipStream_t)stream, accum, out, (int32_t)n,
-                       scale);
+    hipLaunchKernelGGL(tonemap_kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, accum, out, (int32_t)n, scale);
   return check_hip(hipGetLastError(), with_stats ? "tonemap_stats launch" : "tonemap launch");
 }
 
@@ -527,8 +503,7 @@ int ptmi_tile_update(const ptmi_frame* frame, const float* stats, float threshol
   if (int rc = check_stats(stats)) return rc;
   if (!(threshold >= 0.0f)) return fail(PTMI_EINVAL, "threshold must be >= 0");
   if (min_spp < 0 || max_spp < min_spp) return fail(PTMI_EINVAL, "bad spp range [%d, %d]", min_spp, max_spp);
-  if (!tile_state || !tile_err || !tile_list || !n_active || !aligned4(tile_state) || !aligned4(tile_err) ||
-      !aligned4(tile_list) || !aligned4(n_active))
+  if (bad4(tile_state) || bad4(tile_err) || bad4(tile_list) || bad4(n_active))
     return fail(PTMI_EINVAL, "tile buffers NULL/misaligned");
   return check_hip(launch_tile_update(fr, stats, threshold, min_spp, max_spp, tile_state, tile_err, tile_list,
                                       n_active, (hipStream_t)stream),

@@ -2,13 +2,13 @@
 // reprojection (include/ptmi_temporal.h states the contract), shared by the
 // kernel of pt_reproject.hip and the CPU check program reproject_check.cpp.
 //
-// Host/device, no HIP type. A guide pixel is pt_guide_math.hpp's DngG, a stats
+// Host/device, no HIP type. A guide pixel is pt_denoise_math.hpp's DngG, a stats
 // pixel and an accum pixel are RpStats and RpRgb; the caller decides where they
 // are read from. Every operation is f32 with one rounding, in the order written
 // here, so numpy f32 reproduces every value bit for bit
 // (tests/reproject_helpers.py).
 #pragma once
-#include "pt_guide_math.hpp"
+#include "pt_denoise_math.hpp"
 
 namespace ptmi {
 

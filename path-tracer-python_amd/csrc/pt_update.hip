@@ -21,13 +21,11 @@
 // ptmi_prof_*. No render kernel is involved.
 #include <hip/hip_runtime.h>
 
-#include "../../include/ptmi.h"
 #include "../../include/ptmi_update.h"
+#include "pt_args.hpp"
 #include "pt_update_math.hpp"
 
 namespace ptmi {
-
-int set_last_error(int code, const char* msg);  // pt_abi.hip: the text of ptmi_last_error()
 
 constexpr int kUpdBlock = 256;
 constexpr int kRefFloats = 12;   // a ref_nodes row (include/ptmi.h)
@@ -163,8 +161,6 @@ static bool upd_fill(UpdList& d, const ptmi_update_list* s, const float* prims, 
   return d.count >= 0 && d.count <= num_prims;
 }
 
-static bool upd_bad_ptr(const void* p) { return !p || ((uintptr_t)p & 3u); }
-
 }  // namespace ptmi
 
 using namespace ptmi;
@@ -174,50 +170,46 @@ extern "C" {
 int ptmi_update_primitives(const ptmi_scene_view* scene, const ptmi_update_list* spheres,
                            const ptmi_update_list* quads, const ptmi_update_list* tris,
                            const ptmi_update_topology* topo, float* root_box, void* stream) {
-  if (!scene) return set_last_error(PTMI_EINVAL, "update: scene is NULL");
+  if (!scene) return fail(PTMI_EINVAL, "update: scene is NULL");
   if (scene->n_inner < 0 || scene->num_bvh_nodes < 0 || scene->num_spheres < 0 || scene->num_quads < 0 ||
       scene->num_triangles < 0 || (scene->n_inner > 0 && scene->num_bvh_nodes != 2 * scene->n_inner + 1))
-    return set_last_error(PTMI_EINVAL, "update: bad scene counts (num_bvh_nodes must be 2 * n_inner + 1)");
+    return fail(PTMI_EINVAL, "update: bad scene counts (num_bvh_nodes must be 2 * n_inner + 1)");
   UpdList s, q, t;
   if (!upd_fill(s, spheres, scene->spheres, scene->num_spheres, 0, 4, 4))
-    return set_last_error(PTMI_EINVAL, "update: sphere count negative or above num_spheres");
+    return fail(PTMI_EINVAL, "update: sphere count negative or above num_spheres");
   if (!upd_fill(q, quads, scene->quads, scene->num_quads, 2, 16, 9))
-    return set_last_error(PTMI_EINVAL, "update: quad count negative or above num_quads");
+    return fail(PTMI_EINVAL, "update: quad count negative or above num_quads");
   if (!upd_fill(t, tris, scene->tris, scene->num_triangles, 1, 12, 9))
-    return set_last_error(PTMI_EINVAL, "update: triangle count negative or above num_triangles");
+    return fail(PTMI_EINVAL, "update: triangle count negative or above num_triangles");
   const struct {
     const UpdList& l;
-    const char* msg;
-  } lists[3] = {{s, "update: a sphere list pointer is NULL/misaligned"},
-                {q, "update: a quad list pointer is NULL/misaligned"},
-                {t, "update: a triangle list pointer is NULL/misaligned"}};
+    const char* name;
+  } lists[3] = {{s, "sphere"}, {q, "quad"}, {t, "triangle"}};
   for (const auto& e : lists)
-    if (e.l.count > 0 && (upd_bad_ptr(e.l.prim) || upd_bad_ptr(e.l.leaf) || upd_bad_ptr(e.l.row) ||
-                          upd_bad_ptr(e.l.build) || upd_bad_ptr(e.l.prims)))
-      return set_last_error(PTMI_EINVAL, e.msg);
+    if (e.l.count > 0 && (bad4(e.l.prim) || bad4(e.l.leaf) || bad4(e.l.row) || bad4(e.l.build) || bad4(e.l.prims)))
+      return fail(PTMI_EINVAL, "update: a %s list pointer is NULL/misaligned", e.name);
   const int32_t n_inner = scene->n_inner;
   const int64_t n_edits = (int64_t)s.count + q.count + t.count;
-  if ((n_inner > 0 || n_edits > 0) && upd_bad_ptr(scene->ref_nodes))
-    return set_last_error(PTMI_EINVAL, "update: ref_nodes NULL/misaligned");
+  if ((n_inner > 0 || n_edits > 0) && bad4(scene->ref_nodes))
+    return fail(PTMI_EINVAL, "update: ref_nodes NULL/misaligned");
   if (n_inner > 0) {
-    if (!scene->nodes || ((uintptr_t)scene->nodes & 15u))
-      return set_last_error(PTMI_EINVAL, "update: nodes NULL/misaligned");
-    if (!topo) return set_last_error(PTMI_EINVAL, "update: topo is NULL");
-    if (upd_bad_ptr(topo->order)) return set_last_error(PTMI_EINVAL, "update: order NULL/misaligned");
-    if (upd_bad_ptr(topo->slot)) return set_last_error(PTMI_EINVAL, "update: slot NULL/misaligned");
-    if (!root_box || ((uintptr_t)root_box & 3u)) return set_last_error(PTMI_EINVAL, "update: root_box NULL/misaligned");
+    if (bad16(scene->nodes)) return fail(PTMI_EINVAL, "update: nodes NULL/misaligned");
+    if (!topo) return fail(PTMI_EINVAL, "update: topo is NULL");
+    if (bad4(topo->order)) return fail(PTMI_EINVAL, "update: order NULL/misaligned");
+    if (bad4(topo->slot)) return fail(PTMI_EINVAL, "update: slot NULL/misaligned");
+    if (bad4(root_box)) return fail(PTMI_EINVAL, "update: root_box NULL/misaligned");
     if (!topo->level_end || topo->n_levels < 1)
-      return set_last_error(PTMI_EINVAL, "update: level_end is NULL or n_levels < 1");
+      return fail(PTMI_EINVAL, "update: level_end is NULL or n_levels < 1");
     int32_t prev = 0;
     for (int32_t j = 0; j < topo->n_levels; ++j) {
       if (topo->level_end[j] <= prev || topo->level_end[j] > n_inner)
-        return set_last_error(PTMI_EINVAL, "update: level ends must ascend strictly to n_inner");
+        return fail(PTMI_EINVAL, "update: level ends must ascend strictly to n_inner");
       prev = topo->level_end[j];
     }
-    if (prev != n_inner) return set_last_error(PTMI_EINVAL, "update: level ends must ascend strictly to n_inner");
-    if (topo->flags & ~PTMI_UPDATE_ONE_GROUP) return set_last_error(PTMI_EINVAL, "update: unknown flags");
+    if (prev != n_inner) return fail(PTMI_EINVAL, "update: level ends must ascend strictly to n_inner");
+    if (topo->flags & ~PTMI_UPDATE_ONE_GROUP) return fail(PTMI_EINVAL, "update: unknown flags");
     if ((topo->flags & PTMI_UPDATE_ONE_GROUP) && topo->n_levels > PTMI_UPDATE_ONE_GROUP_MAX_LEVELS)
-      return set_last_error(PTMI_EINVAL, "update: too many levels for PTMI_UPDATE_ONE_GROUP");
+      return fail(PTMI_EINVAL, "update: too many levels for PTMI_UPDATE_ONE_GROUP");
   }
   if (scene->num_bvh_nodes == 0) return PTMI_OK;
   hipStream_t st = (hipStream_t)stream;
@@ -242,9 +234,7 @@ int ptmi_update_primitives(const ptmi_scene_view* scene, const ptmi_update_list*
     }
   }
   if (root_box && ref_nodes) hipLaunchKernelGGL(upd_root, dim3(1), dim3(64), 0, st, ref_nodes, root_box);
-  const hipError_t e = hipGetLastError();
-  if (e == hipSuccess) return PTMI_OK;
-  return set_last_error(PTMI_EHIP, hipGetErrorString(e));
+  return hip_result(hipGetLastError());
 }
 
 }  // extern "C"

@@ -18,25 +18,10 @@
 
 #include <vector>
 
+#include "pt_check_io.hpp"
 #include "pt_reproject_math.hpp"
 
 using namespace ptmi;
-
-static bool read_f32(const char* path, std::vector<float>& v) {
-  FILE* f = fopen(path, "rb");
-  if (!f) return false;
-  const size_t got = fread(v.data(), sizeof(float), v.size(), f);
-  const bool at_end = fgetc(f) == EOF;
-  fclose(f);
-  return got == v.size() && at_end;
-}
-
-static bool write_f32(const char* path, const std::vector<float>& v) {
-  FILE* f = fopen(path, "wb");
-  if (!f) return false;
-  const size_t put = fwrite(v.data(), sizeof(float), v.size(), f);
-  return fclose(f) == 0 && put == v.size();
-}
 
 static RpCam camera(const float* s) {
   RpCam c;

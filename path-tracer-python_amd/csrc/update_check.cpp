@@ -19,27 +19,10 @@
 
 #include <vector>
 
+#include "pt_check_io.hpp"
 #include "pt_update_math.hpp"
 
 using namespace ptmi;
-
-static bool read_all(const char* path, std::vector<float>& v) {
-  FILE* f = fopen(path, "rb");
-  if (!f) return false;
-  float buf[1024];
-  size_t got;
-  while ((got = fread(buf, sizeof(float), 1024, f)) > 0) v.insert(v.end(), buf, buf + got);
-  const bool whole = feof(f) && ftell(f) % (long)sizeof(float) == 0;
-  fclose(f);
-  return whole;
-}
-
-static bool write_f32(const char* path, const std::vector<float>& v) {
-  FILE* f = fopen(path, "wb");
-  if (!f) return false;
-  const size_t put = fwrite(v.data(), sizeof(float), v.size(), f);
-  return fclose(f) == 0 && put == v.size();
-}
 
 static void put_box(std::vector<float>& out, const UpdBox& b) {
   out.insert(out.end(), b.mn, b.mn + 3);
@@ -59,7 +42,7 @@ int main(int argc, char** argv) {
     return 2;
   }
   std::vector<float> in, out;
-  if (!read_all(argv[2], in) || in.size() % rec) {
+  if (!read_all_f32(argv[2], in) || in.size() % rec) {
     fprintf(stderr, "cannot read whole records of %zu f32\n", rec);
     return 2;
   }

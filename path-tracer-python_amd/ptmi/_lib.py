@@ -130,6 +130,24 @@ def load(path: str = LIB_PATH):
     return lib
 
 
+_bound = {}  # id of a signature table -> the library it was last bound to
+
+
+def bind(lib, signatures):
+    """Set restype and argtypes of the exports in ``signatures`` (name ->
+    (restype, argtypes)) on ``lib``, once per table and library; a library
+    without one of them raises PtmiError. Returns ``lib``."""
+    if _bound.get(id(signatures)) is not lib:
+        for name, (restype, argtypes) in signatures.items():
+            try:
+                fn = getattr(lib, name)
+            except AttributeError:
+                raise PtmiError(f'libptmi.so has no {name} (rebuild libptmi.so)') from None
+            fn.restype, fn.argtypes = restype, argtypes
+        _bound[id(signatures)] = lib
+    return lib
+
+
 def check(rc: int, what: str):
     if rc != PTMI_OK:
         msg = load().ptmi_last_error().decode(errors='replace')

@@ -37,23 +37,11 @@ def _signatures():
 SIGNATURES = _signatures()
 EXPORTS = tuple(SIGNATURES)
 
-_bound = None
-
 
 def load():
     """libptmi.so (``_lib.load()``) with the guide exports bound; a library
     without them raises PtmiError."""
-    global _bound
-    lib = _lib.load()
-    if _bound is not lib:
-        for name, (restype, argtypes) in SIGNATURES.items():
-            try:
-                fn = getattr(lib, name)
-            except AttributeError:
-                raise _lib.PtmiError(f'libptmi.so has no {name} (rebuild libptmi.so)') from None
-            fn.restype, fn.argtypes = restype, argtypes
-        _bound = lib
-    return lib
+    return _lib.bind(_lib.load(), SIGNATURES)
 
 
 def params(iterations=5, sigma=4.0, sigma_z=0.1, sigma_a=0.2, normal_power_log2=5, demodulate=True):

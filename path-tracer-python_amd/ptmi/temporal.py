@@ -36,23 +36,11 @@ def _signatures():
 SIGNATURES = _signatures()
 EXPORTS = tuple(SIGNATURES)
 
-_bound = None
-
 
 def load():
     """libptmi.so (``_lib.load()``) with the temporal exports bound; a library
     without them raises PtmiError."""
-    global _bound
-    lib = _lib.load()
-    if _bound is not lib:
-        for name, (restype, argtypes) in SIGNATURES.items():
-            try:
-                fn = getattr(lib, name)
-            except AttributeError:
-                raise _lib.PtmiError(f'libptmi.so has no {name} (rebuild libptmi.so)') from None
-            fn.restype, fn.argtypes = restype, argtypes
-        _bound = lib
-    return lib
+    return _lib.bind(_lib.load(), SIGNATURES)
 
 
 def params(max_history=32.0, sigma_z=0.1, normal_min=0.9, sigma_a=0.2):

@@ -27,20 +27,8 @@ def _signatures():
 SIGNATURES = _signatures()
 EXPORTS = tuple(SIGNATURES)
 
-_bound = None
-
 
 def load():
     """libptmi.so (``_lib.load()``) with the listed wavefront export bound; a
     library without it raises PtmiError."""
-    global _bound
-    lib = _lib.load()
-    if _bound is not lib:
-        for name, (restype, argtypes) in SIGNATURES.items():
-            try:
-                fn = getattr(lib, name)
-            except AttributeError:
-                raise _lib.PtmiError(f'libptmi.so has no {name} (rebuild libptmi.so)') from None
-            fn.restype, fn.argtypes = restype, argtypes
-        _bound = lib
-    return lib
+    return _lib.bind(_lib.load(), SIGNATURES)

@@ -42,8 +42,10 @@ def shifted(a, dx, dy, fill):
     return out
 
 
-def one_pass(c, v, step, sigma):
-    sigma = f32(sigma)
+def one_pass(c, v, step, sigma, g=None, sigma_z=0.0, sigma_a=0.0, normal_power_log2=0):
+    """One a-trous pass. With a guide image g (H, W, 8) the tap weight takes the
+    depth, albedo and normal terms of include/ptmi_guide.h as well."""
+    sigma, sigma_z, sigma_a = f32(sigma), f32(sigma_z), f32(sigma_a)
     h, w = v.shape
     with np.errstate(all='ignore'):
         l = lum(c)
@@ -53,13 +55,17 @@ def one_pass(c, v, step, sigma):
         for dy in (-1, 0, 1):
             for dx in (-1, 0, 1):
                 ok = shifted(valid, dx, dy, False)
-                g = G[abs(dx)] * G[abs(dy)]
+                gk = G[abs(dx)] * G[abs(dy)]
                 vq = shifted(v, dx, dy, f32(0))
-                vs = np.where(ok, vs + g * vq, vs)
-                gs = np.where(ok, gs + g, gs)
+                vs = np.where(ok, vs + gk * vq, vs)
+                gs = np.where(ok, gs + gk, gs)
         vbar = vs / gs
         # 2.
         den = sigma * np.sqrt(vbar) + f32(1e-4)
+        if g is not None:
+            den_z = sigma_z * g[..., 3] + f32(1e-4)
+            den_a = sigma_a + f32(1e-4)
+            hit_p = g[..., 7] != 0
         # 3. 5x5 taps at spacing `step`
         C = np.zeros((h, w, 3), f32)
         V, W = np.zeros((h, w), f32), np.zeros((h, w), f32)
@@ -73,6 +79,18 @@ def one_pass(c, v, step, sigma):
                 x = np.abs(l - lq) / den
                 t = np.fmax(f32(0), f32(1) - x)
                 wt = hk * (t * t)
+                if g is not None:
+                    gq = shifted(g, dx * step, dy * step, f32(0))
+                    tz = np.fmax(f32(0), f32(1) - np.abs(g[..., 3] - gq[..., 3]) / den_z)
+                    da = (np.abs(g[..., 4] - gq[..., 4]) + np.abs(g[..., 5] - gq[..., 5])) + np.abs(g[..., 6] - gq[..., 6])
+                    ta = np.fmax(f32(0), f32(1) - da / den_a)
+                    dn = np.fmin(f32(1), np.fmax(f32(0), (g[..., 0] * gq[..., 0] + g[..., 1] * gq[..., 1])
+                                                 + g[..., 2] * gq[..., 2]))
+                    for _ in range(normal_power_log2):
+                        dn = dn * dn
+                    hit_q = gq[..., 7] != 0
+                    wn = np.where(hit_p & hit_q, dn, np.where(~hit_p & ~hit_q, f32(1), f32(0))).astype(f32)
+                    wt = (wt * (tz * tz)) * ((ta * ta) * wn)
                 C = np.where(ok[..., None], C + wt[..., None] * cq, C)
                 V = np.where(ok, V + (wt * wt) * vq, V)
                 W = np.where(ok, W + wt, W)

@@ -8,9 +8,9 @@ plus the index arithmetic, Perlin through ``func_probe('perlin_turb')`` and
 (``sa.mats(type)``) by the oracle's primitive index, so the device's leaf-order
 permutation is no part of the contract.
 
-The guided filter is ``denoise_helpers.one_pass`` extended by the depth, albedo
-and normal terms and the demodulation; ``synthetic_guides`` is a guide image for
-``denoise_helpers.synthetic``."""
+The guided filter is ``denoise_helpers.one_pass`` with a guide image (the depth,
+albedo and normal terms) and the demodulation around it; ``synthetic_guides`` is
+a guide image for ``denoise_helpers.synthetic``."""
 import numpy as np
 
 import denoise_helpers as dh
@@ -147,56 +147,6 @@ def modulation(guides):
     return m, lm * lm
 
 
-def one_pass(c, v, g, step, sigma, sigma_z, sigma_a, normal_power_log2):
-    sigma, sigma_z, sigma_a = f32(sigma), f32(sigma_z), f32(sigma_a)
-    h, w = v.shape
-    with np.errstate(all='ignore'):
-        l = dh.lum(c)
-        valid = dh.finite(l) & dh.finite(v)
-        vs, gs = np.zeros((h, w), f32), np.zeros((h, w), f32)
-        for dy in (-1, 0, 1):
-            for dx in (-1, 0, 1):
-                ok = dh.shifted(valid, dx, dy, False)
-                gk = dh.G[abs(dx)] * dh.G[abs(dy)]
-                vq = dh.shifted(v, dx, dy, f32(0))
-                vs = np.where(ok, vs + gk * vq, vs)
-                gs = np.where(ok, gs + gk, gs)
-        vbar = vs / gs
-        den = sigma * np.sqrt(vbar) + f32(1e-4)
-        den_z = sigma_z * g[..., 3] + f32(1e-4)
-        den_a = sigma_a + f32(1e-4)
-        hit_p = g[..., 7] != 0
-        C = np.zeros((h, w, 3), f32)
-        V, W = np.zeros((h, w), f32), np.zeros((h, w), f32)
-        for dy in range(-2, 3):
-            for dx in range(-2, 3):
-                sx, sy = dx * step, dy * step
-                ok = dh.shifted(valid, sx, sy, False)
-                hk = dh.K[abs(dx)] * dh.K[abs(dy)]
-                lq = dh.shifted(l, sx, sy, f32(0))
-                cq = dh.shifted(c, sx, sy, f32(0))
-                vq = dh.shifted(v, sx, sy, f32(0))
-                gq = dh.shifted(g, sx, sy, f32(0))
-                x = np.abs(l - lq) / den
-                t = np.fmax(f32(0), f32(1) - x)
-                tz = np.fmax(f32(0), f32(1) - np.abs(g[..., 3] - gq[..., 3]) / den_z)
-                da = (np.abs(g[..., 4] - gq[..., 4]) + np.abs(g[..., 5] - gq[..., 5])) + np.abs(g[..., 6] - gq[..., 6])
-                ta = np.fmax(f32(0), f32(1) - da / den_a)
-                dn = np.fmin(f32(1), np.fmax(f32(0), (g[..., 0] * gq[..., 0] + g[..., 1] * gq[..., 1])
-                                             + g[..., 2] * gq[..., 2]))
-                for _ in range(normal_power_log2):
-                    dn = dn * dn
-                hit_q = gq[..., 7] != 0
-                wn = np.where(hit_p & hit_q, dn, np.where(~hit_p & ~hit_q, f32(1), f32(0))).astype(f32)
-                wt = ((hk * (t * t)) * (tz * tz)) * ((ta * ta) * wn)
-                C = np.where(ok[..., None], C + wt[..., None] * cq, C)
-                V = np.where(ok, V + (wt * wt) * vq, V)
-                W = np.where(ok, W + wt, W)
-        c1 = C / W[..., None]
-        v1 = V / (W * W)
-    return (np.where(valid[..., None], c1, c).astype(f32), np.where(valid, v1, v).astype(f32))
-
-
 def denoise_guided(accum, stats, guides, iterations=5, sigma=4.0, sigma_z=0.1, sigma_a=0.2, normal_power_log2=5,
                    demodulate=True):
     """(rgb (H, W, 3), var (H, W)) of ptmi_denoise_guided."""
@@ -207,7 +157,7 @@ def denoise_guided(accum, stats, guides, iterations=5, sigma=4.0, sigma_z=0.1, s
             m, lm2 = modulation(g)
             c, v = c / m, v / lm2
         for i in range(iterations):
-            c, v = one_pass(c, v, g, 1 << i, sigma, sigma_z, sigma_a, normal_power_log2)
+            c, v = dh.one_pass(c, v, 1 << i, sigma, g, sigma_z, sigma_a, normal_power_log2)
         if demodulate:
             c, v = c * m, v * lm2
     return c.astype(f32), v.astype(f32)

@@ -1,8 +1,9 @@
 """CPU tests of the guide ABI (include/ptmi_guide.h): its symbols are in the
 library and in ptmi.guide's own table and in neither of the other two ABIs',
 every rejected argument returns before a HIP call with its message, and the
-guided denoiser's shared arithmetic (csrc/pt_guide_math.hpp, run on the CPU by
-csrc/guide_check.cpp) equals the numpy reference (guide_helpers) bit for bit."""
+guided denoiser's shared arithmetic (csrc/pt_denoise_math.hpp, run on the CPU by
+csrc/denoise_check.cpp, which `make guide_check` builds too) equals the numpy
+reference (guide_helpers) bit for bit."""
 import ctypes as C
 import os
 import re
