@@ -93,6 +93,18 @@ enum {
  *             scene from the shell leaf's own box and sphere alone, without
  *             the two BVH traversals: under 1-3 nothing else can be hit on
  *             either, so results and counters are unchanged bit for bit.
+ *             The same kernels also find, from the hint and the node array
+ *             alone, the chain of ancestors above the shell's leaf: under
+ *             claim 2 each of them has the leaf's box, bit for bit. A segment
+ *             that starts within R / 2 of c begins with up to 6 levels of that
+ *             chain already expanded (the siblings' entries in the pop order
+ *             of the ordinary walk) and, when the whole chain is expanded,
+ *             tests the shell's sphere only if it hit nothing else. A scene
+ *             with a hint may therefore run a kernel with up to 4 more stack
+ *             slots than max_leaf_depth + 1 (at most 20). Results and
+ *             counters are unchanged bit for bit; a chain that cannot be
+ *             found (no child or both children of a node carry the box) is
+ *             not expanded.
  *             Every other kernel (other stack sizes, the stackless and the
  *             reference stack walk, the wavefront) ignores the hint.
  */

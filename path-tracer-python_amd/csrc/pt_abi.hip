@@ -166,6 +166,7 @@ static int to_dev_scene(const ptmi_scene_view* s, DevScene& d) {
   d.ref_nodes = (const float4*)s->ref_nodes;
   d.n_nodes = s->num_bvh_nodes;
   d.shell = s->max_leaf_depth <= 62 ? s->shell : 0;
+  d.max_leaf_depth = s->max_leaf_depth;
   return PTMI_OK;
 }
 

@@ -64,6 +64,7 @@ struct DevScene {
   const float4* __restrict__ tris;
   const float4* __restrict__ mats;
   int32_t mat_base[3];  // indexed by prim type: sphere 0, triangle ns+nq, quad ns
+  int32_t max_leaf_depth;  // root = 0 (the shell chain's slot bound, pt_shell_chain.hpp); in the padding before texels
   const uint32_t* __restrict__ texels;
   int32_t num_images;
   int32_t img_offset[PTMI_MAX_IMAGES], img_w[PTMI_MAX_IMAGES], img_h[PTMI_MAX_IMAGES];
@@ -247,13 +248,22 @@ __device__ __forceinline__ void get_ray(const DevFrame& fr, int32_t px, int32_t 
 // a && b && c && d of per-lane compares as lane masks (v_cmp into SGPR pairs,
 // s_and): the compiler otherwise materialises each compare with v_cndmask and
 // combines them with 16-bit VALU bit ops (~16 VALU per quad test on gfx950)
-__device__ __forceinline__ bool pt_all4(bool a, bool b, bool c, bool d) {
+// (host: the primitive tests below also run on the CPU, shell_chain_check.cpp)
+__host__ __device__ __forceinline__ bool pt_all4(bool a, bool b, bool c, bool d) {
+#if defined(__HIP_DEVICE_COMPILE__)
   return __builtin_amdgcn_inverse_ballot_w64(__builtin_amdgcn_ballot_w64(a) & __builtin_amdgcn_ballot_w64(b) &
                                              __builtin_amdgcn_ballot_w64(c) & __builtin_amdgcn_ballot_w64(d));
+#else
+  return a && b && c && d;
+#endif
 }
 
-__device__ __forceinline__ bool pt_all2(bool a, bool b) {
+__host__ __device__ __forceinline__ bool pt_all2(bool a, bool b) {
+#if defined(__HIP_DEVICE_COMPILE__)
   return __builtin_amdgcn_inverse_ballot_w64(__builtin_amdgcn_ballot_w64(a) & __builtin_amdgcn_ballot_w64(b));
+#else
+  return a && b;
+#endif
 }
 
 // Each returns the candidate t (hit only if returned true); hit point and
@@ -267,7 +277,7 @@ __device__ __forceinline__ bool pt_all2(bool a, bool b) {
 // the current closest t), so the final range test takes t < tmax itself and
 // the caller drops its compare: the same updates, one compare fewer.
 template <bool EXCL = false>
-__device__ __forceinline__ bool hit_sphere_t(const float4 s, pt_v3 o, pt_v3 d, float tmin, float tmax,
+__host__ __device__ __forceinline__ bool hit_sphere_t(const float4 s, pt_v3 o, pt_v3 d, float tmin, float tmax,
                                              float& t) {  // kernels.py:209-248
   pt_v3 c = pt_v3f(s.x, s.y, s.z);
   pt_v3 oc = pt_sub(c, o);
@@ -288,7 +298,7 @@ __device__ __forceinline__ bool hit_sphere_t(const float4 s, pt_v3 o, pt_v3 d, f
 }
 
 template <bool EXCL = false>
-__device__ __forceinline__ bool hit_quad_v(const float4 a, const float4 b, const float4 c, const float4 e, pt_v3 o,
+__host__ __device__ __forceinline__ bool hit_quad_v(const float4 a, const float4 b, const float4 c, const float4 e, pt_v3 o,
                                            pt_v3 d, float tmin, float tmax, float& t) {  // kernels.py:311-362
   pt_v3 n = pt_v3f(a.x, a.y, a.z);
   float denom = pt_dot(n, d);
@@ -320,7 +330,7 @@ __device__ __forceinline__ bool hit_quad_t(const float4* __restrict__ q, pt_v3 o
 }
 
 template <bool EXCL = false>
-__device__ __forceinline__ bool hit_tri_v(const float4 a, const float4 b, const float4 c, pt_v3 o, pt_v3 d,
+__host__ __device__ __forceinline__ bool hit_tri_v(const float4 a, const float4 b, const float4 c, pt_v3 o, pt_v3 d,
                                           float tmin, float tmax, float& t) {  // kernels.py:252-307
   pt_v3 v0 = pt_v3f(a.x, a.y, a.z), e1 = pt_v3f(a.w, b.x, b.y), e2 = pt_v3f(b.z, b.w, c.x);
   pt_v3 hv = pt_cross(d, e2);
@@ -522,23 +532,35 @@ struct Trav {
   __device__ __forceinline__ void init(Stack st) { sp = sp0 = lds_addr(st.slot0); }
 };
 
-template <int STACK, int SB = kBlock>
-__device__ __forceinline__ void trav_begin(const DevScene& sc, Trav& tr, Stack st, pt_v3 d, pt_v3 o, float tmin,
-                                           float tmax) {
+// A segment's ray in the traversal state, stack empty (trav_begin, and the
+// shell chain's expanded begin in pt_megakernel.hip).
+__device__ __forceinline__ void trav_ray(Trav& tr, Stack st, pt_v3 d, float tmin, float tmax) {
   tr.inv = pt_v3f(fabsf(d.x) > 1e-8f ? 1.0f / d.x : 1e8f, fabsf(d.y) > 1e-8f ? 1.0f / d.y : 1e8f,
                   fabsf(d.z) > 1e-8f ? 1.0f / d.z : 1e8f);  // kernels.py:642-646 (Q15)
   tr.tmin = tmin;
   tr.closest = tmax;
   tr.best = 0;
   tr.init(st);
+}
+
+// The root's slab test and entry, for a ray set by trav_ray.
+template <int STACK, int SB = kBlock>
+__device__ __forceinline__ void trav_root(const DevScene& sc, Trav& tr, pt_v3 o) {
   if (sc.n_inner == 0 && sc.root_ref >= 0) return;  // empty scene
   float E, X;
   slab(o, tr.inv, sc.root_min[0], sc.root_min[1], sc.root_min[2], sc.root_max[0], sc.root_max[1], sc.root_max[2],
-       tmin, E, X);
+       tr.tmin, E, X);
   if (pt_minf(X, tr.closest) >= E) {
     lds_store2(tr.sp, (uint32_t)sc.root_ref, __float_as_uint(E));
     tr.sp += SB * 8;
   }
+}
+
+template <int STACK, int SB = kBlock>
+__device__ __forceinline__ void trav_begin(const DevScene& sc, Trav& tr, Stack st, pt_v3 d, pt_v3 o, float tmin,
+                                           float tmax) {
+  trav_ray(tr, st, d, tmin, tmax);
+  trav_root<STACK, SB>(sc, tr, o);
 }
 
 // One step of the traversal loop (one pop); precondition tr.busy().

@@ -24,7 +24,9 @@
 //     (profiles/adaptive/resources.md);
 //   * enclosing medium shell (SHELL): in a scene wrapped in a fog sphere a
 //     path that leaves through it decides its exit search and its last
-//     segment in the shading round of the shell hit, without traversing;
+//     segment in the shading round of the shell hit, without traversing, and
+//     a segment from inside the shell begins with the shell's ancestor chain
+//     already expanded (pt_shell_chain.hpp);
 //   * BVH: child-box BVH2 nodes (80 B, one node load tests both children),
 //     traversal stack in LDS (slot-major, conflict-free), see pt_device.hpp.
 // Perlin corner loop fully unrolled here (A/B on MI355X: +2.5 % megakernel,
@@ -34,6 +36,7 @@
 #endif
 #include "pt_launch.hpp"
 #include "pt_prof.hpp"
+#include "pt_shell_chain.hpp"
 
 namespace ptmi {
 
@@ -163,6 +166,15 @@ constexpr int kMkBlock = 64;
 // the tuning constants of its launch shape are in pt_mk_plan.hpp.
 constexpr int kMkTile = 8;
 
+// Node floats for the shell chain (pt_shell_chain.hpp) through the constant
+// address space, as load_shell_box reads them: uniform offsets, scalar loads.
+struct ChainLoad {
+  const float4* nodes;
+  __device__ __forceinline__ uint32_t operator()(uint32_t off, uint32_t i) const {
+    return *(const __attribute__((address_space(4))) uint32_t*)((uintptr_t)nodes + off + 4u * i);
+  }
+};
+
 template <int STACK, bool STAGED, int TRAV = PTMI_TRAV_STACK, bool LISTED = false, bool SHELL = false>
 // waves/SIMD the LDS stack allows: 160 KiB / (STACK * 8 B * 256) blocks per CU
 // (16 -> 5, 20 -> 4, 24 -> 3, 32 -> 2), and the VGPR budget of that many
@@ -284,9 +296,47 @@ __global__ __launch_bounds__(kMkBlock, stress_waves(STACK < 20 ? PTMI_MK_MIN_WAV
   tr.init(st);
   bool trav = false;  // a segment is in flight (traversal running or result pending)
   bool need_seg = false;  // begin a segment after this pass's refill
+  // SHELL: the chain of ancestors above the shell's leaf, all with the leaf's
+  // box (pt_shell_chain.hpp), found once per wave from scalar
+  // loads in converged code; cplan: the levels STACK slots allow. A segment
+  // that starts within the gate (the inline shell's, R / 2 of the centre)
+  // begins with those levels expanded; with the shell's leaf skipped, the
+  // shading round tests it for a lane that hit nothing else.
+  ShellChain chain{};
+  ShellPlan cplan{0, false};
+  float4 csph = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // the shell's sphere (cplan.m > 0)
+  const ChainLoad cld{sc.nodes};
+  if constexpr (SHELL) {
+    chain = shell_chain_find(cld, sc.shell, sc.n_inner, sc.root_ref);
+    cplan = shell_chain_plan(chain, STACK, sc.max_leaf_depth);
+    if (cplan.m > 0) {
+      const Shell sh = load_shell_box(sc);
+      // the leaf the traversal would load as a sphere, nothing else (a wrong hint expands nothing)
+      if (sh.ref < 0 && leaf_type(sh.ref) == kSphere && leaf_class(sh.ref) == PTMI_CLASS_MEDIUM)
+        csph = load_shell_sphere(sc, sh);
+      else
+        cplan = ShellPlan{0, false};
+    }
+  }
   auto begin_segment = [&]() {
     const bool em = ps.mode == kModeMediumExit;
-    trav_begin<STACK, kMkBlock>(sc, tr, st, ps.dir, ps.o, em ? ps.t_entry + 0.0001f : kTMin, kTMax);  // :418/:1057
+    const float tmin = em ? ps.t_entry + 0.0001f : kTMin;  // :418/:1057
+    bool root = true;  // the ordinary begin
+    if constexpr (SHELL) {
+      if (cplan.m > 0) {  // wave-uniform
+        root = false;
+        trav_ray(tr, st, ps.dir, tmin, kTMax);
+        const pt_v3 oc = pt_sub(ps.o, pt_v3f(csph.x, csph.y, csph.z));
+        bool ex = false;
+        if (4.0f * pt_dot(oc, oc) <= csph.w * csph.w)  // the gate
+          ex = shell_chain_begin(cld, chain, cplan, ps.o, ps.dir, tr.inv, tr.tmin, tr.closest, [&](uint32_t ref, float E) {
+            lds_store2(tr.sp, ref, __float_as_uint(E));
+            tr.sp += kMkBlock * 8;
+          });
+        if (!ex) trav_root<STACK, kMkBlock>(sc, tr, ps.o);
+      }
+    }
+    if (root) trav_begin<STACK, kMkBlock>(sc, tr, st, ps.dir, ps.o, tmin, kTMax);
     if (em) ++n_med; else ++n_seg;
     trav = true;
   };
@@ -384,6 +434,25 @@ __global__ __launch_bounds__(kMkBlock, stress_waves(STACK < 20 ? PTMI_MK_MIN_WAV
     PT_P4(1)  // wave turbulence
     if (shade_now) {  // segment traced: shade it
       trav = false;
+      if constexpr (SHELL) {
+        // the skipped shell leaf: a segment that began expanded (the gate, from
+        // ps.o, which only shading changes) and hit nothing else tests it now,
+        // as its leaf step would have with closest still at kTMax; if the
+        // shared box failed its slab test the segment began at the root, found
+        // the same miss, and shell_hit fails on that box again
+        if (cplan.skip && !tr.any()) {
+          const pt_v3 oc = pt_sub(ps.o, pt_v3f(csph.x, csph.y, csph.z));
+          if (4.0f * pt_dot(oc, oc) <= csph.w * csph.w) {
+            Shell s0 = load_shell_box(sc);
+            s0.sph = csph;
+            float te;
+            if (shell_hit(s0, ps.o, ps.dir, tr.inv, tr.tmin, te)) {
+              tr.closest = te;
+              tr.best = s0.ref;
+            }
+          }
+        }
+      }
       bool exit_mode = ps.mode == kModeMediumExit;
       bool hit = tr.any();
       float t = tr.closest;
@@ -706,8 +775,11 @@ static hipError_t launch_mk(const DevScene& sc, const DevFrame& fr, float* accum
   return hipGetLastError();
 }
 
-// The SHELL kernels exist for the stack walk at 16 to 20 slots (vol2's 16, the
-// fine rungs up to C4-sized BVHs); every other rung ignores the scene's hint.
+// The SHELL kernels exist for the stack walk at 16 to 20 slots (vol2's 20 with
+// its chain expanded, shell_chain_stack_request; the fine rungs up to C4-sized
+// BVHs); every other rung ignores the scene's hint. A/B on MI355X against the
+// parent commit, bit-identical: C2 +3.1 %, C5 +3.2 % (DESIGN.md §12a,
+// profiles/chain/bench_parent_vs_new.json).
 // Not at 19 slots: with the flag that kernel takes 135 VGPRs, past the
 // 128 of its 4 waves/SIMD (profiles/shell/resources.md), and no scene here
 // runs it to say whether that pays.
@@ -716,6 +788,7 @@ constexpr bool kMkShellRung = TRAV == PTMI_TRAV_STACK && STACK >= 16 && STACK <=
 
 hipError_t mk_render(const DevScene& sc, const DevFrame& fr, int32_t stack_needed, float* accum,
                      int32_t s_begin, int32_t s_count, unsigned long long* counters, hipStream_t stream) {
+  if (sc.shell != 0) stack_needed = shell_chain_stack_request(stack_needed);  // room for the expanded chain
   // SHELL wraps the ladder, plain kernels first (see mk_trace_staged)
   auto render = [&](auto shell) {
     return dispatch_traversal<false>(fr, stack_needed, [&](auto stack, auto trav) {
@@ -761,6 +834,7 @@ static hipError_t launch_mk_trace(const DevScene& sc, const DevFrame& fr, float*
 hipError_t mk_trace_staged(const DevScene& sc, const DevFrame& fr, int32_t stack_needed, void* ws,
                            const int32_t* tile_list, int32_t n, int32_t s_begin, int32_t nb,
                            unsigned long long* counters, hipStream_t stream) {
+  if (sc.shell != 0) stack_needed = shell_chain_stack_request(stack_needed);  // room for the expanded chain
   // LISTED wraps the ladder rather than branching inside its callable, unlisted
   // first: the code object then holds the unlisted kernels before the listed
   // ones, rung by rung, as it always has.
