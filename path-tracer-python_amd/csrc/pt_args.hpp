@@ -1,5 +1,6 @@
 // pt_args.hpp — the argument checks every entry point of libptmi.so shares
-// (pt_abi.hip, pt_denoise.hip, pt_guide.hip, pt_reproject.hip, pt_update.hip).
+// (pt_abi.hip, pt_denoise.hip, pt_guide.hip, pt_reproject.hip, pt_motion.hip,
+// pt_update.hip).
 // Host only. The text of ptmi_last_error() and the render prologue are
 // pt_abi.hip's; the rest is inline.
 #pragma once
@@ -41,6 +42,34 @@ inline int64_t image_pixels(int32_t width, int32_t height) {
 inline bool overlaps(const void* a, uint64_t a_bytes, const void* b, uint64_t b_bytes) {
   const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
   return x < y + b_bytes && y < x + a_bytes;
+}
+
+// The name of the first device array of a checked scene view (include/ptmi.h's
+// layouts) that [p, p + bytes) overlaps, or NULL: for a call that writes an
+// image while it reads the scene.
+inline const char* scene_overlap(const ptmi_scene_view* s, const void* p, uint64_t bytes) {
+  uint64_t texels = 0;
+  for (int32_t k = 0; k < s->num_images && k < PTMI_MAX_IMAGES; ++k) {
+    const uint64_t end = (uint64_t)s->img_offset[k] + (uint64_t)s->img_w[k] * (uint64_t)s->img_h[k];
+    if (end > texels) texels = end;
+  }
+  const uint64_t prims = (uint64_t)s->num_spheres + (uint64_t)s->num_quads + (uint64_t)s->num_triangles;
+  const struct {
+    const char* name;
+    const void* p;
+    uint64_t bytes;
+  } parts[] = {{"nodes", s->nodes, (uint64_t)s->n_inner * (uint64_t)ptmi_node_bytes()},
+               {"spheres", s->spheres, 16 * (uint64_t)s->num_spheres},
+               {"quads", s->quads, 64 * (uint64_t)s->num_quads},
+               {"tris", s->tris, 48 * (uint64_t)s->num_triangles},
+               {"mats", s->mats, 80 * prims},
+               {"texels", s->texels, 4 * texels},
+               {"perlin_vec", s->perlin_vec, 256 * 16},
+               {"perlin_perm", s->perlin_perm, 3 * 256 * 4},
+               {"ref_nodes", s->ref_nodes, 48 * (uint64_t)s->num_bvh_nodes}};
+  for (const auto& part : parts)
+    if (part.p && part.bytes && overlaps(p, bytes, part.p, part.bytes)) return part.name;
+  return nullptr;
 }
 
 }  // namespace ptmi

@@ -1,6 +1,8 @@
 // pt_check_io.hpp — the raw little-endian f32 files of the CPU check programs
-// (denoise_check.cpp, reproject_check.cpp, update_check.cpp). Host only.
+// (denoise_check.cpp, reproject_check.cpp, update_check.cpp, motion_check.cpp).
+// Host only.
 #pragma once
+#include <stdint.h>
 #include <stdio.h>
 
 #include <vector>
@@ -10,6 +12,16 @@ inline bool read_f32(const char* path, std::vector<float>& v) {
   FILE* f = fopen(path, "rb");
   if (!f) return false;
   const size_t got = fread(v.data(), sizeof(float), v.size(), f);
+  const bool at_end = fgetc(f) == EOF;
+  fclose(f);
+  return got == v.size() && at_end;
+}
+
+// The same for raw little-endian i32 (motion_check.cpp's id images).
+inline bool read_i32(const char* path, std::vector<int32_t>& v) {
+  FILE* f = fopen(path, "rb");
+  if (!f) return false;
+  const size_t got = fread(v.data(), sizeof(int32_t), v.size(), f);
   const bool at_end = fgetc(f) == EOF;
   fclose(f);
   return got == v.size() && at_end;

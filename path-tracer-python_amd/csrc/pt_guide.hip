@@ -9,10 +9,17 @@
 //     pixel is written as two 16-B stores. No cross-lane reads beyond those
 //     inside traverse()'s leaf tests.
 //
+//   * guide_trace<STACK, TRAV, true>: the same kernel, which also writes the id
+//     of the surface a pixel describes (ptmi_guide_trace_ids,
+//     include/ptmi_motion.h): one more dword store per pixel. The id image is a
+//     trailing kernel argument that the plain form does not have, so the plain
+//     instantiations are what they were (profiles/motion/resources.md).
+//
 // Not timed by ptmi_prof_*.
 #include <hip/hip_runtime.h>
 
 #include "../../include/ptmi_guide.h"
+#include "../../include/ptmi_motion.h"
 #include "pt_args.hpp"
 #include "pt_image.hpp"
 #include "pt_launch.hpp"
@@ -24,10 +31,12 @@ constexpr int kGuideSquare = 8;
 constexpr int kGuideTraversals = 4;
 constexpr float kGuideMissDepth = 1e10f;
 
-template <int STACK, int TRAV>
+// IDS: the trailing argument is the id image, int32_t* (an id form takes it, a plain one nothing).
+template <int STACK, int TRAV, bool IDS = false, class... Ids>
 __global__ __launch_bounds__(kGuideBlock, stress_waves(1)) void guide_trace(DevScene sc, DevFrame fr,
                                                                             float4* __restrict__ guides,
-                                                                            int32_t squares_x) {
+                                                                            int32_t squares_x, Ids... ids) {
+  static_assert(sizeof...(Ids) == (IDS ? 1 : 0), "an id form takes its id image, a plain one nothing");
   __shared__ uint2 lds_stack[STACK * kGuideBlock];
   const int tid = threadIdx.x;
   Stack st{lds_stack + tid};
@@ -77,18 +86,36 @@ __global__ __launch_bounds__(kGuideBlock, stress_waves(1)) void guide_trace(DevS
   const size_t p = (size_t)py * (size_t)fr.width + (size_t)px;
   guides[2 * p] = gn;
   guides[2 * p + 1] = ga;
+  if constexpr (IDS) {
+    // the leaf code without bit 31 and the class bits: type << 28 | prim
+    int32_t* __restrict__ out = (ids, ...);
+    out[p] = surface ? (leaf_type(ref) << 28 | leaf_index(ref)) : -1;
+  }
 }
 
+// ids: the id image of the id form, or no argument.
+template <class... Ids>
 static hipError_t launch_guide_trace(const DevScene& sc, const DevFrame& fr, int32_t stack_needed, float* guides,
-                                     hipStream_t stream) {
+                                     hipStream_t stream, Ids... ids) {
   const int32_t squares_x = image_tiles_x(fr.width, kGuideSquare);
   const dim3 squares = image_tile_grid(fr.width, fr.height, kGuideSquare);  // < 2^31 / 3 pixels / 64 + edges
   return dispatch_traversal<false>(fr, stack_needed, [&](auto stack, auto trav) {
     constexpr int S = decltype(stack)::value, T = decltype(trav)::value;
-    hipLaunchKernelGGL((guide_trace<S, T>), squares, dim3(kGuideBlock), 0, stream, sc, fr,
-                       (float4*)guides, squares_x);
+    hipLaunchKernelGGL((guide_trace<S, T, sizeof...(Ids) != 0, Ids...>), squares, dim3(kGuideBlock), 0, stream, sc, fr,
+                       (float4*)guides, squares_x, ids...);
     return hipGetLastError();
   });
+}
+
+// ptmi_guide_trace's checks, under the name of the entry point that makes them.
+static int guide_trace_args(const char* what, const ptmi_scene_view* scene, const ptmi_frame* frame,
+                            const float* guides, DevScene& sc, DevFrame& fr) {
+  if (int rc = to_dev(scene, frame, sc, fr)) return rc;
+  if (bad16(guides)) return fail(PTMI_EINVAL, "%s: guides NULL/misaligned", what);
+  if (fr.x0 != 0 || fr.y0 != 0 || fr.w != fr.width || fr.h != fr.height)
+    return fail(PTMI_EINVAL, "%s: the frame is windowed (guides are whole-frame)", what);
+  if (fr.band_stride != 1) return fail(PTMI_EINVAL, "%s: the frame is banded (guides are whole-frame)", what);
+  return PTMI_OK;
 }
 
 }  // namespace ptmi
@@ -100,12 +127,21 @@ extern "C" {
 int ptmi_guide_trace(const ptmi_scene_view* scene, const ptmi_frame* frame, float* guides, void* stream) {
   DevScene sc;
   DevFrame fr;
-  if (int rc = to_dev(scene, frame, sc, fr)) return rc;
-  if (bad16(guides)) return fail(PTMI_EINVAL, "guide_trace: guides NULL/misaligned");
-  if (fr.x0 != 0 || fr.y0 != 0 || fr.w != fr.width || fr.h != fr.height)
-    return fail(PTMI_EINVAL, "guide_trace: the frame is windowed (guides are whole-frame)");
-  if (fr.band_stride != 1) return fail(PTMI_EINVAL, "guide_trace: the frame is banded (guides are whole-frame)");
+  if (int rc = guide_trace_args("guide_trace", scene, frame, guides, sc, fr)) return rc;
   return hip_result(launch_guide_trace(sc, fr, stack_needed(scene), guides, (hipStream_t)stream));
+}
+
+int ptmi_guide_trace_ids(const ptmi_scene_view* scene, const ptmi_frame* frame, float* guides, int32_t* ids,
+                         void* stream) {
+  DevScene sc;
+  DevFrame fr;
+  if (int rc = guide_trace_args("guide_trace_ids", scene, frame, guides, sc, fr)) return rc;
+  if (bad4(ids)) return fail(PTMI_EINVAL, "guide_trace_ids: ids NULL/misaligned");
+  const uint64_t n = (uint64_t)fr.width * (uint64_t)fr.height;
+  if (overlaps(ids, 4 * n, guides, 32 * n)) return fail(PTMI_EINVAL, "guide_trace_ids: ids aliases guides");
+  if (const char* part = scene_overlap(scene, ids, 4 * n))
+    return fail(PTMI_EINVAL, "guide_trace_ids: ids aliases the scene's %s", part);
+  return hip_result(launch_guide_trace(sc, fr, stack_needed(scene), guides, (hipStream_t)stream, ids));
 }
 
 }  // extern "C"

@@ -16,9 +16,8 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/ptmi_temporal.h"
-#include "pt_args.hpp"
 #include "pt_image.hpp"
-#include "pt_reproject_math.hpp"
+#include "pt_reproject_args.hpp"
 
 namespace ptmi {
 
@@ -54,17 +53,6 @@ __global__ __launch_bounds__(kImgBlock) void rp_reproject(RpCam cur, RpCam prev,
   a[2] = o.accum.b;
 }
 
-static RpCam rp_cam(const ptmi_camera* c) {
-  RpCam r;
-  for (int k = 0; k < 3; ++k) {
-    r.center[k] = c->center[k];
-    r.pixel00[k] = c->pixel00[k];
-    r.delta_u[k] = c->delta_u[k];
-    r.delta_v[k] = c->delta_v[k];
-  }
-  return r;
-}
-
 static hipError_t launch_reproject(const RpCam& cur, const RpCam& prev, const RpParams& prm, const float* guides_cur,
                                    const float* guides_prev, const float* accum_prev, const float* stats_prev,
                                    int32_t width, int32_t height, float* accum_out, float* stats_out,
@@ -84,43 +72,18 @@ extern "C" {
 int ptmi_reproject(const ptmi_camera* cur, const ptmi_camera* prev, const float* guides_cur, const float* guides_prev,
                    const float* accum_prev, const float* stats_prev, int32_t width, int32_t height,
                    const ptmi_reproject_params* params, float* accum_out, float* stats_out, void* stream) {
-  if (!cur || !prev) return fail(PTMI_EINVAL, "reproject: a camera is NULL");
-  if (bad16(guides_cur)) return fail(PTMI_EINVAL, "reproject: guides_cur NULL/misaligned");
-  if (bad16(guides_prev)) return fail(PTMI_EINVAL, "reproject: guides_prev NULL/misaligned");
-  if (!accum_prev) return fail(PTMI_EINVAL, "reproject: accum_prev is NULL");
-  if (bad16(stats_prev)) return fail(PTMI_EINVAL, "reproject: stats_prev NULL/misaligned");
-  if (!params) return fail(PTMI_EINVAL, "reproject: params is NULL");
-  if (!accum_out) return fail(PTMI_EINVAL, "reproject: accum_out is NULL");
-  if (bad16(stats_out)) return fail(PTMI_EINVAL, "reproject: stats_out NULL/misaligned");
-  const uint64_t n = (uint64_t)image_pixels(width, height);
-  if (n == 0)
-    return fail(PTMI_EINVAL, "reproject: bad image size (width and height >= 1, at most 2^31-1 pixels)");
-  const struct {
-    const char* name;
-    const void* p;
-    uint64_t bytes;
-  } in[4] = {{"guides_cur", guides_cur, 32 * n},
-             {"guides_prev", guides_prev, 32 * n},
-             {"accum_prev", accum_prev, 12 * n},
-             {"stats_prev", stats_prev, 16 * n}};
-  for (const auto& i : in) {
-    if (overlaps(accum_out, 12 * n, i.p, i.bytes)) return fail(PTMI_EINVAL, "reproject: accum_out aliases %s", i.name);
-    if (overlaps(stats_out, 16 * n, i.p, i.bytes)) return fail(PTMI_EINVAL, "reproject: stats_out aliases %s", i.name);
-  }
-  if (overlaps(accum_out, 12 * n, stats_out, 16 * n))
-    return fail(PTMI_EINVAL, "reproject: accum_out aliases stats_out");
-  if (!(params->max_history >= 1.0f && params->max_history <= kRpMaxHistory))
-    return fail(PTMI_EINVAL, "reproject: max_history must be in [1, 2^24]");
-  if (!(params->sigma_z >= 0.0f)) return fail(PTMI_EINVAL, "reproject: sigma_z must be >= 0");
-  if (!(params->normal_min >= -1.0f && params->normal_min <= 1.0f))
-    return fail(PTMI_EINVAL, "reproject: normal_min must be in [-1, 1]");
-  if (!(params->sigma_a >= 0.0f)) return fail(PTMI_EINVAL, "reproject: sigma_a must be >= 0");
-  if (params->flags != 0) return fail(PTMI_EINVAL, "reproject: flags must be 0");
+  uint64_t n = 0;
+  if (int rc = reproject_pointer_args("reproject", cur, prev, guides_cur, guides_prev, accum_prev, stats_prev, width,
+                                      height, params, accum_out, stats_out, n))
+    return rc;
+  const RpBuffer in[4] = {{"guides_cur", guides_cur, 32 * n},
+                          {"guides_prev", guides_prev, 32 * n},
+                          {"accum_prev", accum_prev, 12 * n},
+                          {"stats_prev", stats_prev, 16 * n}};
+  if (int rc = reproject_overlap_args("reproject", in, 4, accum_out, stats_out, n)) return rc;
   RpParams prm;
-  prm.max_history = params->max_history;
-  prm.sigma_z = params->sigma_z;
-  prm.normal_min = params->normal_min;
-  prm.sigma_a = params->sigma_a;
+  if (int rc = reproject_param_args("reproject", params, prm)) return rc;
+  if (params->flags != 0) return fail(PTMI_EINVAL, "reproject: flags must be 0");
   return hip_result(launch_reproject(rp_cam(cur), rp_cam(prev), prm, guides_cur, guides_prev, accum_prev, stats_prev,
                                      width, height, accum_out, stats_out, (hipStream_t)stream));
 }

@@ -1,6 +1,8 @@
 // pt_reproject_math.hpp — the per-pixel arithmetic of the temporal
 // reprojection (include/ptmi_temporal.h states the contract), shared by the
 // kernel of pt_reproject.hip and the CPU check program reproject_check.cpp.
+// Steps 1, 2 and 3 - 7 are separate functions: the motion-aware reprojection
+// (pt_motion_math.hpp) puts its own step 2' between them.
 //
 // Host/device, no HIP type. A guide pixel is pt_denoise_math.hpp's DngG, a stats
 // pixel and an accum pixel are RpStats and RpRgb; the caller decides where they
@@ -47,34 +49,45 @@ PTMI_DN_HD RpV3 rp_cross(RpV3 a, RpV3 b) {
   return RpV3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
 }
 
-// Pixel (px, py) of the current frame. guide_cur(x, y) returns the current
-// frame's guide pixel (called once, for (px, py)); guide_prev, accum_prev and
-// stats_prev return the previous frame's pixels and are called only for
-// coordinates inside the image: stats first, accum and guide only for a tap
-// whose count is at least 2.
-template <class GuideCur, class GuidePrev, class AccumPrev, class StatsPrev>
-PTMI_DN_HD RpOut rp_reproject_px(int32_t px, int32_t py, int32_t width, int32_t height, const RpCam& cur,
-                                 const RpCam& prev, const RpParams& prm, GuideCur&& guide_cur, GuidePrev&& guide_prev,
-                                 AccumPrev&& accum_prev, StatsPrev&& stats_prev) {
-  RpOut out = {};  // a pixel without history: all zeros
+// Step 1: the primary ray of ptmi_guide_trace through pixel (px, py).
+struct RpRay {
+  RpV3 c, d;  // origin (the camera centre) and direction, not normalised
+  float len;  // sqrtf(dot(d, d))
+};
 
-  // 1. the primary ray of ptmi_guide_trace
+PTMI_DN_HD RpRay rp_primary_ray(int32_t px, int32_t py, const RpCam& cur) {
   const RpV3 c = rp_v3(cur.center), p00 = rp_v3(cur.pixel00), du = rp_v3(cur.delta_u), dv = rp_v3(cur.delta_v);
   const float fpx = (float)px, fpy = (float)py;
   const RpV3 ps = {(p00.x + du.x * fpx) + dv.x * fpy, (p00.y + du.y * fpx) + dv.y * fpy,
                    (p00.z + du.z * fpx) + dv.z * fpy};
   const RpV3 d = rp_sub(ps, c);
-  const float len = sqrtf(rp_dot(d, d));
+  return RpRay{c, d, sqrtf(rp_dot(d, d))};
+}
 
-  // 2. the surface point seen from the previous camera, or the direction of a miss
-  const DngG g = guide_cur(px, py);
-  const bool hit_p = g.hit != 0.0f;
-  RpV3 v = d;
-  if (hit_p) {
-    const float s = g.z / len;
-    const RpV3 P = {c.x + d.x * s, c.y + d.y * s, c.z + d.z * s};
-    v = rp_sub(P, rp_v3(prev.center));
-  }
+// Step 2's surface point P of a hit pixel at guide depth `depth`.
+PTMI_DN_HD RpV3 rp_surface_point(const RpRay& ray, float depth) {
+  const float s = depth / ray.len;
+  return RpV3{ray.c.x + ray.d.x * s, ray.c.y + ray.d.y * s, ray.c.z + ray.d.z * s};
+}
+
+// The tap predicate of a reprojection that has none.
+struct RpEveryTap {
+  PTMI_DN_HD bool operator()(int32_t, int32_t) const { return true; }
+};
+
+// Steps 3 - 7 for a current pixel whose guide pixel is g: v is step 2's vector
+// from the previous camera (to the surface point for a hit, the ray direction
+// for a miss), hit_p whether the pixel is a hit. guide_prev, accum_prev and
+// stats_prev return the previous frame's pixels and are called only for
+// coordinates inside the image: stats first, accum and guide only for a tap
+// whose count is at least 2. tap_ok(qx, qy) is a further condition on the taps
+// of a hit pixel (include/ptmi_motion.h's step 5'), asked before the tap's
+// guide pixel is read.
+template <class GuidePrev, class AccumPrev, class StatsPrev, class TapOk>
+PTMI_DN_HD RpOut rp_history_px(RpV3 v, bool hit_p, const DngG& g, int32_t width, int32_t height, const RpCam& prev,
+                               const RpParams& prm, GuidePrev&& guide_prev, AccumPrev&& accum_prev,
+                               StatsPrev&& stats_prev, TapOk&& tap_ok) {
+  RpOut out = {};  // a pixel without history: all zeros
 
   // 3. its pixel position (a, b) in the previous frame
   const RpV3 pdu = rp_v3(prev.delta_u), pdv = rp_v3(prev.delta_v);
@@ -110,6 +123,7 @@ PTMI_DN_HD RpOut rp_reproject_px(int32_t px, int32_t py, int32_t width, int32_t 
       const float cr = acc.r * scale, cg = acc.g * scale, cb = acc.b * scale;
       const float s2 = st.m2 / (st.n - 1.0f);
       if (!(dn_finite(cr) && dn_finite(cg) && dn_finite(cb) && dn_finite(s2))) continue;
+      if (hit_p && !tap_ok(qx, qy)) continue;
       const DngG gq = guide_prev(qx, qy);
       if ((gq.hit != 0.0f) != hit_p) continue;
       if (hit_p) {
@@ -139,6 +153,25 @@ PTMI_DN_HD RpOut rp_reproject_px(int32_t px, int32_t py, int32_t width, int32_t 
   out.accum = RpRgb{cm.r * n, cm.g * n, cm.b * n};
   out.stats = RpStats{n, dn_lum(cm), s2m * (n - 1.0f), 0.0f};
   return out;
+}
+
+// Pixel (px, py) of the current frame: steps 1 and 2, then rp_history_px.
+// guide_cur(x, y) returns the current frame's guide pixel (called once, for
+// (px, py)).
+template <class GuideCur, class GuidePrev, class AccumPrev, class StatsPrev>
+PTMI_DN_HD RpOut rp_reproject_px(int32_t px, int32_t py, int32_t width, int32_t height, const RpCam& cur,
+                                 const RpCam& prev, const RpParams& prm, GuideCur&& guide_cur, GuidePrev&& guide_prev,
+                                 AccumPrev&& accum_prev, StatsPrev&& stats_prev) {
+  // 1. the primary ray of ptmi_guide_trace
+  const RpRay ray = rp_primary_ray(px, py, cur);
+
+  // 2. the surface point seen from the previous camera, or the direction of a miss
+  const DngG g = guide_cur(px, py);
+  const bool hit_p = g.hit != 0.0f;
+  RpV3 v = ray.d;
+  if (hit_p) v = rp_sub(rp_surface_point(ray, g.z), rp_v3(prev.center));
+
+  return rp_history_px(v, hit_p, g, width, height, prev, prm, guide_prev, accum_prev, stats_prev, RpEveryTap{});
 }
 
 }  // namespace ptmi

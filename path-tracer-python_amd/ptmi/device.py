@@ -15,7 +15,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib, guide, post, temporal, update, wf_tiles
+from . import _lib, guide, motion, post, temporal, update, wf_tiles
 from .scene_data import (DeviceLayout, PRIM_QUAD, PRIM_SPHERE, PRIM_TRIANGLE, SceneArrays, camera_upload,
                          fill_node_boxes, pack_device, shell_hint)
 
@@ -105,6 +105,15 @@ class DeviceScene:
     @classmethod
     def from_arrays(cls, sa: SceneArrays, device=None):
         return cls(sa, device)
+
+    def primitive_rows(self, stream=None):
+        """Device-to-device copies of the sphere, quad and triangle row tensors,
+        ``(spheres, quads, tris)``: the "previous rows" of a motion-aware
+        reprojection (Integrator.reproject_moved), taken before an update.
+        Asynchronous on ``stream``."""
+        with torch.cuda.device(self.device), torch.cuda.stream(
+                stream if stream is not None else torch.cuda.current_stream(self.device)):
+            return self.t_spheres.clone(), self.t_quads.clone(), self.t_tris.clone()
 
     # ------------------------------------------------ scene updates (ptmi.update)
     def _update_state(self):
@@ -710,6 +719,71 @@ class Integrator:
                        'ptmi_reproject')
         return out_accum, out_stats
 
+    # ------------------------------------------------ motion-aware reprojection (ptmi.motion)
+    def trace_guides_ids(self, frame, out=None, stream=None):
+        """``trace_guides`` that also returns which primitive each pixel sees
+        (ptmi_guide_trace_ids, include/ptmi_motion.h): ``(guides, ids)``, the
+        guides byte for byte ``trace_guides``', ids an (H, W) int32 tensor of
+        ``type << 28 | device primitive index`` on surface hits and -1
+        elsewhere. ``out``: a (guides, ids) pair to write into."""
+        lib = motion.load()
+        dev = self.scene.device
+        h, w = int(frame.height), int(frame.width)
+        with self._dev():
+            if out is None:
+                out = (torch.empty((h, w, guide.GUIDE_CHANNELS), dtype=torch.float32, device=dev),
+                       torch.empty((h, w), dtype=torch.int32, device=dev))
+            guides, ids = out
+            _check_guides(guides, h, w, dev)
+            _check_ids(ids, h, w, dev)
+            _lib.check(lib.ptmi_guide_trace_ids(self.scene.view, frame, guides.data_ptr(), ids.data_ptr(),
+                                                self._stream(stream)), 'ptmi_guide_trace_ids')
+        return guides, ids
+
+    def reproject_moved(self, cur_cam, prev_cam, guides_cur, guides_prev, ids_cur, ids_prev, prev_rows, accum, stats, *,
+                        max_history=32.0, sigma_z=0.1, normal_min=0.9, sigma_a=0.2, match_ids=True, out=None,
+                        stream=None):
+        """``reproject`` across a scene update (ptmi_reproject_moved,
+        include/ptmi_motion.h): a hit pixel's surface point is first carried to
+        where it was on its primitive before the update, by the primitive's
+        current row (this scene's) and its previous row (``prev_rows``, the
+        ``DeviceScene.primitive_rows()`` taken before the update); with
+        ``match_ids`` a tap must also show the same primitive. ``ids_cur`` and
+        ``ids_prev`` are ``trace_guides_ids``' id images of the two frames.
+        Everything else, the return value included, is ``reproject``'s."""
+        lib = motion.load()
+        dev = self.scene.device
+        h, w = self._check_denoise_inputs(accum, stats)
+        _check_guides(guides_cur, h, w, dev)
+        _check_guides(guides_prev, h, w, dev)
+        _check_ids(ids_cur, h, w, dev)
+        _check_ids(ids_prev, h, w, dev)
+        rows = tuple(prev_rows)
+        if len(rows) != 3:
+            raise _lib.PtmiError('prev_rows must be (spheres, quads, tris)')
+        for t, mine, name in zip(rows, (self.scene.t_spheres, self.scene.t_quads, self.scene.t_tris),
+                                 ('spheres', 'quads', 'tris')):
+            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.is_contiguous()
+                    and t.device == dev and t.shape == mine.shape):
+                raise _lib.PtmiError(f'prev_rows: {name} must be a contiguous float32 tensor of {mine.numel()} values '
+                                     f'on {dev} (DeviceScene.primitive_rows())')
+        cur, prev = temporal.camera(cur_cam), temporal.camera(prev_cam)
+        prm = motion.params(max_history, sigma_z, normal_min, sigma_a, match_ids)
+        with self._dev():
+            if out is None:
+                out = (torch.empty_like(accum), torch.empty_like(stats))
+            out_accum, out_stats = out
+            self._check_denoise_inputs(out_accum, out_stats)
+            if tuple(out_accum.shape) != tuple(accum.shape):
+                raise _lib.PtmiError(f'out must be an (accum, stats) pair of a {w} x {h} image')
+            _lib.check(lib.ptmi_reproject_moved(C.byref(cur), C.byref(prev), guides_cur.data_ptr(),
+                                                guides_prev.data_ptr(), accum.data_ptr(), stats.data_ptr(),
+                                                ids_cur.data_ptr(), ids_prev.data_ptr(), self.scene.view,
+                                                rows[0].data_ptr(), rows[1].data_ptr(), rows[2].data_ptr(), w, h,
+                                                C.byref(prm), out_accum.data_ptr(), out_stats.data_ptr(),
+                                                self._stream(stream)), 'ptmi_reproject_moved')
+        return out_accum, out_stats
+
     def _after_traces(self, stream):
         """Make `stream` wait for the overlapped traces in flight: they add to
         the counters from their side streams."""
@@ -767,6 +841,14 @@ def _check_guides(guides, height, width, device=None):
         raise _lib.PtmiError(f'guides must be a contiguous cuda float32 tensor of shape {shape}')
     if device is not None and guides.device != device:
         raise _lib.PtmiError(f'guides is on {guides.device}, the scene on {device}')
+
+
+def _check_ids(ids, height, width, device=None):
+    if not (isinstance(ids, torch.Tensor) and ids.is_cuda and ids.dtype == torch.int32 and ids.is_contiguous()
+            and tuple(ids.shape) == (height, width)):
+        raise _lib.PtmiError(f'ids must be a contiguous cuda int32 tensor of shape ({height}, {width})')
+    if device is not None and ids.device != device:
+        raise _lib.PtmiError(f'ids is on {ids.device}, the scene on {device}')
 
 
 def _check_accum(accum, frame, device=None):

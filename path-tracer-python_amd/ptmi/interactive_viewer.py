@@ -20,6 +20,10 @@ samples are batched.
 the reference): a camera move reprojects the accumulated history to the new
 camera instead of clearing it. The default, temporal=False, is
 the behaviour above, bit for bit.
+
+``InteractiveViewer(..., temporal=True, motion=True)``: a scene update
+(``update_primitives``) keeps the history too, carried to where every surface
+point went. The default, motion=False, drops it as before.
 """
 from __future__ import annotations
 
@@ -55,7 +59,10 @@ def orbit_step(theta, phi, delta_x, delta_y, velocity=(0.3, 0.3)):
 
 
 class InteractiveViewer(MI355XRenderer):
-    def __init__(self, world, cam, img_path: str, temporal: bool = False, max_history: float = 32, **kwargs):
+    def __init__(self, world, cam, img_path: str, temporal: bool = False, max_history: float = 32,
+                 motion: bool = False, **kwargs):
+        if motion and not temporal:
+            raise ValueError('motion=True keeps the temporal history across scene updates: it needs temporal=True')
         super().__init__(world, cam, img_path, **kwargs)
         # temporal=True: a camera move reprojects the accumulated history to the
         # new camera instead of clearing it (MI355XRenderer.reproject_history,
@@ -66,6 +73,13 @@ class InteractiveViewer(MI355XRenderer):
         self._sample_origin = 0  # RNG sample index of current_sample == 0: rises across restarts
         self._history_cam = None  # camera and guides of the last render: what the rendered history was seen with
         self._history_guides = None
+        # motion=True: update_primitives carries the history across the update
+        # (MI355XRenderer.reproject_history with prev_ids / prev_rows, DESIGN.md
+        # §18). The id image of the last render, and, once the scene has been
+        # updated since that render, the primitive rows it was rendered with.
+        self.motion = bool(motion)
+        self._history_ids = None
+        self._history_rows = None
         self._history_kept = False  # the last restart reprojected: the next render keeps accum / stats
         self.mouse_down = False
         self.last_mouse_x = 0
@@ -103,9 +117,9 @@ class InteractiveViewer(MI355XRenderer):
         in a temporal viewer, the samples rendered before the restarts."""
         return self._sample_origin + self.current_sample
 
-    def _restart_with_history(self):
+    def _restart_with_history(self, what='Camera rotated'):
         """The temporal restart: the rendered history reprojected to the
-        camera uploaded since. _history_cam / _history_guides stay those of the
+        camera uploaded (and, in a motion viewer, the scene updated) since. _history_cam / _history_guides stay those of the
         last camera samples were rendered at, so a further restart with no
         sample in between (the next step of one drag) reprojects that same
         rendered history again (reproject_history(again=True)) instead of
@@ -117,12 +131,14 @@ class InteractiveViewer(MI355XRenderer):
         self.current_sample = 0
         self.sample_times = []
         self.render_start_time = time.time()
+        # the scene was updated since the history was rendered: the motion-aware form, by the rows it had then
+        moved = dict(prev_ids=self._history_ids, prev_rows=self._history_rows) if self._history_rows is not None else {}
         self.history_fraction = self.reproject_history(self._history_cam, self._history_guides, again=again,
-                                                       max_history=self.max_history)
+                                                       max_history=self.max_history, **moved)
         self._history_kept = True
         self.integrator.reset_counters()
         self.is_rendering_active = True
-        print(f"\n{'─' * 60}\nCamera rotated - history reprojected to {100.0 * self.history_fraction:.1f}% of the "
+        print(f"\n{'─' * 60}\n{what} - history reprojected to {100.0 * self.history_fraction:.1f}% of the "
               f"pixels (at most {self.max_history:g} samples each)\n{'─' * 60}")
 
     def restart_rendering(self):
@@ -141,11 +157,22 @@ class InteractiveViewer(MI355XRenderer):
         print(f"\n{'─' * 60}\nCamera rotated - restarting render from sample 0\n{'─' * 60}")
 
     def update_primitives(self, spheres=None, quads=None, triangles=None):
-        """MI355XRenderer.update_primitives; the temporal history is dropped
-        with the image: there are no motion vectors, so a surface point of the
-        old scene says nothing about the new one."""
+        """MI355XRenderer.update_primitives. Without ``motion`` the temporal
+        history is dropped with the image. A ``motion=True``
+        viewer that has a rendered history keeps it: the update runs, and the
+        history is reprojected from the camera, guides, ids and primitive rows
+        it was rendered with to the current camera and scene,
+        by the rule of ``_restart_with_history``: a second update, or a camera
+        move, with no sample in between reprojects the rendered history again,
+        not the reprojected one."""
+        if self.motion and self.stats is not None and self._history_guides is not None and \
+                self._history_ids is not None and (self.current_sample > 0 or self._history_kept):
+            if self._history_rows is None:  # the scene still is what the history was rendered with
+                self._history_rows = self.dscene.primitive_rows()
+            self._apply_update(spheres, quads, triangles)
+            return self._restart_with_history('Scene updated')
         super().update_primitives(spheres, quads, triangles)
-        self._history_cam = self._history_guides = None
+        self._history_cam = self._history_guides = self._history_ids = self._history_rows = None
         self._history_kept = False
         self.history_fraction = None
         self.render_start_time = time.time()
@@ -219,7 +246,11 @@ class InteractiveViewer(MI355XRenderer):
                 self._adaptive = None  # no pass schedule: not resumable as a render_adaptive() run
                 self._adaptive_reset()
         if self.temporal:  # the guides of this camera, traced once: what a later restart reprojects by
-            self._history_cam, self._history_guides = self.frame.cam, self.guides()
+            if self.motion:
+                self._history_guides, self._history_ids = self.guides_ids()
+            else:
+                self._history_guides = self.guides()
+            self._history_cam, self._history_rows = self.frame.cam, None
             self._history_kept = False
         self.integrator.reset_counters()
         print(f'  Kernel Warmup: {(time.time() - t0) * 1000:6.2f}ms')

@@ -101,6 +101,9 @@ class MI355XRenderer:
         self._guides = None
         self._guides_key = None
         self.guide_trace_seconds = None
+        # guides_ids(): the id image that goes with the guides, under the same key
+        self._ids = None
+        self._ids_key = None
         # reproject_history(): the (accum, stats) pair it writes into next, swapped with the live pair on each call
         self._history_spare = None
         # update_primitives(): bumped on every scene update; part of the guides' cache key
@@ -345,6 +348,29 @@ class MI355XRenderer:
             self._guides_key = key
         return self._guides
 
+    def guides_ids(self):
+        """``(guides, ids)`` of the current camera (Integrator.trace_guides_ids,
+        include/ptmi_motion.h): the guides of ``guides()`` and an (height,
+        width) int32 tensor naming the primitive each pixel sees (``type << 28
+        | device primitive index``, -1 where no surface shows). Traced once per
+        camera and scene and cached like ``guides()``, whose tensor it fills
+        or reuses."""
+        key = self._guide_key()
+        if self._ids is None or self._ids_key != key:
+            import torch
+            have = self._guides if self._guides is not None and self._guides_key == key else None
+            ids = torch.empty((int(self.frame.height), int(self.frame.width)), dtype=torch.int32,
+                              device=self.integrator.scene.device)
+            t0 = time.time()
+            out = (have if have is not None else torch.empty(tuple(ids.shape) + (8,), dtype=torch.float32,
+                                                             device=ids.device), ids)
+            self._guides, self._ids = self.integrator.trace_guides_ids(self.frame, out=out)
+            torch.cuda.synchronize(self.integrator.scene.device)
+            if have is None:
+                self.guide_trace_seconds = time.time() - t0
+            self._guides_key = self._ids_key = key
+        return self._guides, self._ids
+
     def guide_maps(self):
         """The guides as numpy AOVs: {'normal': (H, W, 3), 'depth': (H, W),
         'albedo': (H, W, 3), 'hit': (H, W) bool}; depth is 1e10 where hit is False."""
@@ -361,7 +387,7 @@ class MI355XRenderer:
 
     _REBUILD = 'for any other edit build a new MI355XRenderer from the edited world'
 
-    def update_primitives(self, spheres=None, quads=None, triangles=None):
+    def update_primitives(self, spheres=None, quads=None, triangles=None, keep_history=False, **params):
         """Move primitives of the resident scene and refit its BVH on the device
         (DeviceScene.update_primitives, include/ptmi_update.h).
         Each argument maps a reference primitive index (the primitive's place
@@ -376,7 +402,42 @@ class MI355XRenderer:
         is reset as for a new adaptive render, ``denoised`` and the
         reprojection spare pair are dropped, and the guides are retraced on
         their next use. ``arrays`` is afterwards what the device holds, with
-        the geometry arrays of a full compile of the edited world."""
+        the geometry arrays of a full compile of the edited world.
+
+        ``keep_history=True`` (a stats render is needed, a ValueError
+        otherwise) carries the image across the update instead
+        (include/ptmi_motion.h): the guides, the id image and a
+        copy of the primitive rows are taken before the update, the guides and
+        ids are retraced after it, and ``reproject_history`` moves ``accum``
+        and ``stats`` to where every surface point went, with ``params`` as
+        its parameters. The accumulator is not cleared and ``current_sample``
+        stays; the tile states start over and ``denoised`` is dropped. Returns
+        the fraction of pixels with history (None without keep_history)."""
+        if keep_history:
+            if self.stats is None:
+                raise ValueError('keep_history=True needs stats: render through the stats path (render_adaptive) first')
+            prev_cam = self.frame.cam
+            prev_guides, prev_ids = self.guides_ids()
+            prev_rows = self.dscene.primitive_rows()
+        elif params:
+            raise ValueError(f'{sorted(params)} are reprojection parameters: they need keep_history=True')
+        self._apply_update(spheres, quads, triangles)
+        if keep_history:
+            return self.reproject_history(prev_cam, prev_guides, prev_ids=prev_ids, prev_rows=prev_rows, **params)
+        self.clear_accumulation_buffer()
+        self.current_sample = 0
+        self.sample_times = []
+        self.adaptive_passes = []
+        if self.stats is not None:
+            self._adaptive_reset()
+        self.denoised = self.denoised_var = self.denoise_seconds = None
+        self._history_spare = None
+        self._guides = None
+        self.integrator.reset_counters()
+
+    def _apply_update(self, spheres, quads, triangles):
+        """update_primitives' checks and the update itself, up to the bumped
+        ``scene_revision``; what becomes of the image is the caller's."""
         kinds = {'spheres': ('Sphere', 'sphere_mats', lambda o: o.material, lambda o: o.center.at(0.0)),
                  'quads': ('quad', 'quad_mats', lambda o: o.mat, lambda o: o.Q),
                  'triangles': ('triangle', 'tri_mats', lambda o: o.mat, lambda o: o.v0)}
@@ -407,18 +468,9 @@ class MI355XRenderer:
                 self._prims[name][i] = obj
         self.arrays = self.dscene.arrays
         self.scene_revision += 1
-        self.clear_accumulation_buffer()
-        self.current_sample = 0
-        self.sample_times = []
-        self.adaptive_passes = []
-        if self.stats is not None:
-            self._adaptive_reset()
-        self.denoised = self.denoised_var = self.denoise_seconds = None
-        self._history_spare = None
-        self._guides = None
-        self.integrator.reset_counters()
 
-    def reproject_history(self, prev_camera, prev_guides, again=False, **params):
+    def reproject_history(self, prev_camera, prev_guides, again=False, prev_ids=None, prev_rows=None, match_ids=True,
+                          **params):
         """Carry ``accum`` and ``stats`` of a stats render from ``prev_camera``
         (its camera-upload dict or ptmi_camera) with the guides ``prev_guides``
         it had to the current camera (Integrator.reproject,
@@ -434,24 +486,42 @@ class MI355XRenderer:
         spare pair; ``prev_camera`` and ``prev_guides`` are still its own) is
         reprojected to the current camera and replaces that call's result, so
         a drag of many steps resamples and caps the rendered history once, not
-        once per step. Derived state: not checkpointed."""
+        once per step. Derived state: not checkpointed.
+
+        ``prev_ids`` and ``prev_rows``, both or neither (one alone is a
+        ValueError): the id image the history's frame had (``guides_ids()``)
+        and the primitive rows of its scene (``DeviceScene.primitive_rows()``),
+        for a scene updated since. The reprojection is then the motion-aware
+        one (Integrator.reproject_moved, include/ptmi_motion.h, DESIGN.md
+        §18), with ``match_ids`` as its flag."""
         if self.stats is None:
             raise ValueError('no stats: render through the stats path (render_adaptive) first')
+        if (prev_ids is None) != (prev_rows is None):
+            raise ValueError('prev_ids and prev_rows go together: the id image and the primitive rows of the '
+                             'history\'s frame')
         import torch
-        guides = self.guides()
+        if prev_ids is None:
+            guides = self.guides()
+            reproject = self.integrator.reproject
+        else:
+            guides, ids = self.guides_ids()
+
+            def reproject(cur, prev, g_cur, g_prev, accum, stats, **kw):
+                return self.integrator.reproject_moved(cur, prev, g_cur, g_prev, ids, prev_ids, prev_rows, accum,
+                                                       stats, match_ids=match_ids, **kw)
         spare = self._history_spare
         if spare is not None and tuple(spare[0].shape) != tuple(self.accum.shape):
             spare = None
         if again:
             if spare is None:
                 raise ValueError('again=True needs an earlier reproject_history() of this image size')
-            self.integrator.reproject(self.frame.cam, prev_camera, guides, prev_guides, spare[0], spare[1],
-                                      out=(self.accum, self.stats), **params)
+            reproject(self.frame.cam, prev_camera, guides, prev_guides, spare[0], spare[1],
+                      out=(self.accum, self.stats), **params)
         else:
             if spare is None:
                 spare = (torch.empty_like(self.accum), torch.empty_like(self.stats))
-            out = self.integrator.reproject(self.frame.cam, prev_camera, guides, prev_guides, self.accum, self.stats,
-                                            out=spare, **params)
+            out = reproject(self.frame.cam, prev_camera, guides, prev_guides, self.accum, self.stats, out=spare,
+                            **params)
             self._history_spare = (self.accum, self.stats)
             self.accum, self.stats = out
         self._tiles = self.integrator.new_tiles(self.frame)
