@@ -13,6 +13,7 @@
 #include "../../include/ptmi.h"
 #include "../../include/ptmi_math.h"
 #include "../../include/ptmi_rng.h"
+#include "pt_shell_chain.hpp"
 
 namespace ptmi {
 
@@ -998,35 +999,25 @@ typedef const __attribute__((address_space(4))) float pt_cf;
 typedef float pt_f4v __attribute__((ext_vector_type(4)));  // clang vector type: no C++ copy constructor
 typedef const __attribute__((address_space(4))) pt_f4v pt_cf4;
 
-// Wave-uniform: the node at the hint's byte offset (checked on the host), child
-// 0 or 1 of it. The sphere is left to the caller, which loads it
-// (load_shell_sphere) only for a lane whose traversal hit this very leaf as a
-// sphere, a load the traversal itself made, so a wrong hint reads nothing out
-// of bounds.
-__device__ __forceinline__ Shell load_shell_box(const DevScene& sc) {
-  const uint32_t v = (uint32_t)sc.shell - 1u, c = v & 1u;
-  // constant address space: the scene is read-only while a kernel runs, and a
-  // uniform address there is fetched by the scalar unit into SGPRs, not by 64
-  // lanes through the texture-address unit, the megakernel's busiest (DESIGN.md
-  // §5). A/B on MI355X against plain pointers, same bits: C2 +0.3 %, C5 +0.5 %,
-  // every run above every run (profiles/shell/bench_parent_vs_new.json)
-  const pt_cf* nd = (const pt_cf*)((uintptr_t)sc.nodes + (v & ~1u));
+// The shell's leaf box, leaf code and sphere from the wave's table
+// (pt_shell_chain.hpp: built once per wave from the node at the hint's byte
+// offset, checked on the host, and from the sphere that leaf names; the sphere
+// entries are 0 unless the leaf is a sphere, so a wrong hint reads nothing out
+// of bounds). tl(i) is dword i; the megakernel's reads lanes of two VGPRs and
+// must run with all 64 lanes active.
+template <class T>
+__device__ __forceinline__ Shell shell_from_table(const T& tl) {
   Shell sh;
-  sh.lox = nd[0 + c];
-  sh.loy = nd[2 + c];
-  sh.loz = nd[4 + c];
-  sh.hix = nd[6 + c];
-  sh.hiy = nd[8 + c];
-  sh.hiz = nd[10 + c];
-  sh.ref = __float_as_int(nd[12 + c]);
-  sh.sph = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  sh.lox = __uint_as_float(tl(kTabLeaf + 0));
+  sh.loy = __uint_as_float(tl(kTabLeaf + 1));
+  sh.loz = __uint_as_float(tl(kTabLeaf + 2));
+  sh.hix = __uint_as_float(tl(kTabLeaf + 3));
+  sh.hiy = __uint_as_float(tl(kTabLeaf + 4));
+  sh.hiz = __uint_as_float(tl(kTabLeaf + 5));
+  sh.ref = (int32_t)tl(kTabLeaf + 6);
+  sh.sph = make_float4(__uint_as_float(tl(kTabSphere + 0)), __uint_as_float(tl(kTabSphere + 1)),
+                       __uint_as_float(tl(kTabSphere + 2)), __uint_as_float(tl(kTabSphere + 3)));
   return sh;
-}
-
-// The shell's sphere, for a lane whose hit is the shell's leaf (uniform address).
-__device__ __forceinline__ float4 load_shell_sphere(const DevScene& sc, const Shell& sh) {
-  const pt_f4v s = *(const pt_cf4*)((uintptr_t)sc.spheres + 16u * (uint32_t)leaf_index(sh.ref));
-  return make_float4(s.x, s.y, s.z, s.w);
 }
 
 // Closest hit in [tmin, kTMax) of a ray that can hit nothing but the shell.

@@ -167,11 +167,43 @@ constexpr int kMkBlock = 64;
 constexpr int kMkTile = 8;
 
 // Node floats for the shell chain (pt_shell_chain.hpp) through the constant
-// address space, as load_shell_box reads them: uniform offsets, scalar loads.
+// address space (the scene is read-only while a kernel runs): scalar loads at
+// the uniform offsets of shell_chain_find, per-lane loads where each lane
+// fetches its own table entry (shell_table_entry).
 struct ChainLoad {
   const float4* nodes;
   __device__ __forceinline__ uint32_t operator()(uint32_t off, uint32_t i) const {
     return *(const __attribute__((address_space(4))) uint32_t*)((uintptr_t)nodes + off + 4u * i);
+  }
+};
+// Float a of the sphere a leaf code names; 0 unless it is a sphere leaf.
+struct ChainSphereLoad {
+  const float4* spheres;
+  __device__ __forceinline__ uint32_t operator()(int32_t ref, int a) const {
+    if (!(ref < 0 && leaf_type(ref) == kSphere)) return 0u;
+    return *(const __attribute__((address_space(4))) uint32_t*)((uintptr_t)spheres + 16u * (uint32_t)leaf_index(ref) +
+                                                                 4u * (uint32_t)a);
+  }
+};
+// The wave's shell table (pt_shell_chain.hpp): lane i holds dwords i and
+// 64 + i. A read is a v_readlane at a lane number known at compile time; the
+// VGPRs may be spilled (the 16- to 18-slot kernels spill some) and a reload
+// under a partial EXEC mask would leave stale lanes, so every read sits in
+// converged code.
+// A/B on MI355X against the same 81 values computed in the prologue as uniform
+// values that the compiler keeps or spills (DESIGN.md §12's "not tried"): the
+// table C2 +5.0 %, C5 +3.9 % over the parent, that variant +0.6 % and +1.5 %
+// (profiles/shell_table/bench_parent_vs_new.json); not kept.
+struct ShellTable {
+  uint32_t t0, t1;
+  __device__ __forceinline__ uint32_t operator()(int i) const {
+    return (uint32_t)__builtin_amdgcn_readlane((int)(i < 64 ? t0 : t1), i & 63);
+  }
+  template <class L, class S>
+  __device__ __forceinline__ void build(const L& ld, const S& sl, const ShellChain& ch, const ShellPlan& p, int32_t shell,
+                                        int32_t n_inner, int lane) {
+    t0 = shell_table_entry(ld, sl, ch, p, shell, n_inner, lane);
+    t1 = shell_table_entry(ld, sl, ch, p, shell, n_inner, 64 + lane);
   }
 };
 
@@ -302,45 +334,62 @@ __global__ __launch_bounds__(kMkBlock, stress_waves(STACK < 20 ? PTMI_MK_MIN_WAV
   // that starts within the gate (the inline shell's, R / 2 of the centre)
   // begins with those levels expanded; with the shell's leaf skipped, the
   // shading round tests it for a lane that hit nothing else.
+  // Everything the expanded begin and the shading round's shell tests read
+  // (the chain's sibling boxes, centres and refs, the shell's leaf box, code
+  // and sphere) is fetched here once, each lane its own entries, into the
+  // wave's table: it follows a device refit, and no pass of the loop loads it
+  // again. Kept across the loop: the table's two VGPRs, the chain's side bits
+  // and the plan.
   ShellChain chain{};
   ShellPlan cplan{0, false};
-  float4 csph = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // the shell's sphere (cplan.m > 0)
-  const ChainLoad cld{sc.nodes};
+  ShellTable stab{};
   if constexpr (SHELL) {
+    const ChainLoad cld{sc.nodes};
     chain = shell_chain_find(cld, sc.shell, sc.n_inner, sc.root_ref);
     cplan = shell_chain_plan(chain, STACK, sc.max_leaf_depth);
+    stab.build(cld, ChainSphereLoad{sc.spheres}, chain, cplan, sc.shell, sc.n_inner, lane);
     if (cplan.m > 0) {
-      const Shell sh = load_shell_box(sc);
+      const int32_t ref = (int32_t)stab(kTabLeaf + 6);
       // the leaf the traversal would load as a sphere, nothing else (a wrong hint expands nothing)
-      if (sh.ref < 0 && leaf_type(sh.ref) == kSphere && leaf_class(sh.ref) == PTMI_CLASS_MEDIUM)
-        csph = load_shell_sphere(sc, sh);
-      else
-        cplan = ShellPlan{0, false};
+      if (!(ref < 0 && leaf_type(ref) == kSphere && leaf_class(ref) == PTMI_CLASS_MEDIUM)) cplan = ShellPlan{0, false};
     }
   }
-  auto begin_segment = [&]() {
+  // SHELL kernels call it converged, `on` marking the lanes that begin a
+  // segment: the table is read across lanes, so the expanded begin runs with
+  // all 64 lanes active and `on` (then the gate) predicates what it writes.
+  auto begin_segment = [&](bool on) {
     const bool em = ps.mode == kModeMediumExit;
     const float tmin = em ? ps.t_entry + 0.0001f : kTMin;  // :418/:1057
-    bool root = true;  // the ordinary begin
+    bool root = on;  // the ordinary begin
     if constexpr (SHELL) {
       if (cplan.m > 0) {  // wave-uniform
         root = false;
-        trav_ray(tr, st, ps.dir, tmin, kTMax);
-        const pt_v3 oc = pt_sub(ps.o, pt_v3f(csph.x, csph.y, csph.z));
+        if (on) trav_ray(tr, st, ps.dir, tmin, kTMax);
+        const pt_v3 oc = pt_sub(ps.o, pt_v3f(__uint_as_float(stab(kTabSphere + 0)), __uint_as_float(stab(kTabSphere + 1)),
+                                             __uint_as_float(stab(kTabSphere + 2))));
+        const float cr = __uint_as_float(stab(kTabSphere + 3));
+        const bool gate = on && 4.0f * pt_dot(oc, oc) <= cr * cr;
         bool ex = false;
-        if (4.0f * pt_dot(oc, oc) <= csph.w * csph.w)  // the gate
-          ex = shell_chain_begin(cld, chain, cplan, ps.o, ps.dir, tr.inv, tr.tmin, tr.closest, [&](uint32_t ref, float E) {
-            lds_store2(tr.sp, ref, __float_as_uint(E));
-            tr.sp += kMkBlock * 8;
-          });
-        if (!ex) trav_root<STACK, kMkBlock>(sc, tr, ps.o);
+        if (pt_ballot(gate) != 0ull)  // wave-uniform: EXEC stays full inside
+          ex = shell_chain_begin(stab, chain, cplan, ps.o, ps.dir, tr.inv, tr.tmin, tr.closest, gate,
+                                 [&](uint32_t ref, float E) {
+                                   lds_store2(tr.sp, ref, __float_as_uint(E));
+                                   tr.sp += kMkBlock * 8;
+                                 });
+        if (on && !ex) trav_root<STACK, kMkBlock>(sc, tr, ps.o);
       }
     }
     if (root) trav_begin<STACK, kMkBlock>(sc, tr, st, ps.dir, ps.o, tmin, kTMax);
-    if (em) ++n_med; else ++n_seg;
-    trav = true;
+    if (on) {
+      if (em) ++n_med; else ++n_seg;
+      trav = true;
+    }
   };
-  if (live) begin_segment();
+  if constexpr (SHELL) {  // a wave-uniform branch around the converged begin
+    if (pt_ballot(live) != 0ull) begin_segment(live);
+  } else if (live) {
+    begin_segment(true);
+  }
 
 #if PTMI_PROBE == 4
   // shading-round probe (diagnostic build, tools/probe.py --sections): wave
@@ -432,6 +481,10 @@ __global__ __launch_bounds__(kMkBlock, stress_waves(STACK < 20 ? PTMI_MK_MIN_WAV
     int32_t ruv = kRuvNone, sref = 0;
     float4 m0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // the metal's albedo and fuzz (scatter_end)
     PT_P4(1)  // wave turbulence
+    // SHELL: the shell's leaf box, leaf code and sphere for this round's three
+    // tests, read from the wave's table here, in converged code
+    Shell shl{};
+    if constexpr (SHELL) shl = shell_from_table(stab);
     if (shade_now) {  // segment traced: shade it
       trav = false;
       if constexpr (SHELL) {
@@ -441,14 +494,12 @@ __global__ __launch_bounds__(kMkBlock, stress_waves(STACK < 20 ? PTMI_MK_MIN_WAV
         // shared box failed its slab test the segment began at the root, found
         // the same miss, and shell_hit fails on that box again
         if (cplan.skip && !tr.any()) {
-          const pt_v3 oc = pt_sub(ps.o, pt_v3f(csph.x, csph.y, csph.z));
-          if (4.0f * pt_dot(oc, oc) <= csph.w * csph.w) {
-            Shell s0 = load_shell_box(sc);
-            s0.sph = csph;
+          const pt_v3 oc = pt_sub(ps.o, pt_v3f(shl.sph.x, shl.sph.y, shl.sph.z));
+          if (4.0f * pt_dot(oc, oc) <= shl.sph.w * shl.sph.w) {
             float te;
-            if (shell_hit(s0, ps.o, ps.dir, tr.inv, tr.tmin, te)) {
+            if (shell_hit(shl, ps.o, ps.dir, tr.inv, tr.tmin, te)) {
               tr.closest = te;
-              tr.best = s0.ref;
+              tr.best = shl.ref;
             }
           }
         }
@@ -458,7 +509,7 @@ __global__ __launch_bounds__(kMkBlock, stress_waves(STACK < 20 ? PTMI_MK_MIN_WAV
       float t = tr.closest;
       const int32_t ref = tr.best;
       int32_t g = -1;
-      Shell sh{};          // SHELL: the shell's leaf box and sphere
+      const Shell& sh = shl;  // SHELL: the shell's leaf box and sphere
       bool inl = false;    // SHELL: this lane resolves its exit search (and escape segment) here
       if (!exit_mode) {
         if (!hit) {
@@ -470,9 +521,7 @@ __global__ __launch_bounds__(kMkBlock, stress_waves(STACK < 20 ? PTMI_MK_MIN_WAV
             ps.t_entry = t;
             ps.ref_entry = ref;
             if constexpr (SHELL) {
-              sh = load_shell_box(sc);
               if (ref == sh.ref && leaf_type(ref) == kSphere) {
-                sh.sph = load_shell_sphere(sc, sh);
                 const pt_v3 oc = pt_sub(ps.o, pt_v3f(sh.sph.x, sh.sph.y, sh.sph.z));
                 inl = 4.0f * pt_dot(oc, oc) <= sh.sph.w * sh.sph.w;  // the gate: the segment began within R / 2 of the centre
               }
@@ -652,9 +701,12 @@ __global__ __launch_bounds__(kMkBlock, stress_waves(STACK < 20 ? PTMI_MK_MIN_WAV
         }
       }
       PT_P4(5)  // refill: unit fetch, bind, camera ray
-      if (need_seg) {
+      if constexpr (SHELL) {
+        if (pt_ballot(need_seg) != 0ull) begin_segment(need_seg);
         need_seg = false;
-        begin_segment();
+      } else if (need_seg) {
+        need_seg = false;
+        begin_segment(true);
       }
       PT_P4(6)  // segment begin (inverse direction, root slab)
 #if PTMI_PROBE == 2
@@ -678,9 +730,12 @@ __global__ __launch_bounds__(kMkBlock, stress_waves(STACK < 20 ? PTMI_MK_MIN_WAV
 #endif
       if (__ballot(live) == 0ull && drained && next >= wend) break;
     } else {
-      if (need_seg) {
+      if constexpr (SHELL) {
+        if (pt_ballot(need_seg) != 0ull) begin_segment(need_seg);
         need_seg = false;
-        begin_segment();
+      } else if (need_seg) {
+        need_seg = false;
+        begin_segment(true);
       }
       if (__ballot(live) == 0ull) break;
     }

@@ -13,10 +13,16 @@
 // expanded begin, and whether the finish tested the skipped shell. The first
 // line of stdout is the chain: m, full, side, the plan for STACK slots (m,
 // skip), the slot bound, then the m node offsets. Exit 0 iff the files were
-// read and written and no walk overflowed kCap slots.
+// read and written and no walk overflowed kCap slots. A twelfth argument
+// `table` builds the wave's table (shell_table_entry) in an array of 128
+// dwords first, as the megakernel does in two VGPRs, runs the expanded begin
+// and the finish from that array alone, and prints the table's kTabSize dwords
+// (hex) as a second line. Without it every table entry is computed from the
+// node array where it is read.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include <vector>
 
@@ -38,6 +44,22 @@ struct Scene {
 struct Load {
   const std::vector<float>* nodes;
   uint32_t operator()(uint32_t off, uint32_t i) const { return pt_chain_u((*nodes)[off / 4u + i]); }
+};
+
+// float a of the sphere a leaf code names, 0 unless it is a sphere leaf of the array (ChainSphereLoad, pt_megakernel.hip)
+struct SphereLoad {
+  const std::vector<float>* spheres;
+  uint32_t operator()(int32_t ref, int a) const {
+    const size_t ix = (size_t)(ref & 0x01ffffff);
+    if (!(ref < 0 && ((ref >> 28) & 3) == kSphere) || 4 * ix + 4 > spheres->size()) return 0u;
+    return pt_chain_u((*spheres)[4 * ix + (size_t)a]);
+  }
+};
+
+// the table in an array, as the megakernel keeps it in two VGPRs
+struct TableLoad {
+  const uint32_t* t;
+  uint32_t operator()(int i) const { return t[i]; }
 };
 
 struct Entry {
@@ -154,8 +176,10 @@ void begin_root(const Scene& sc, Walk& w) {  // trav_begin: the root's box is it
 }  // namespace
 
 int main(int argc, char** argv) {
-  if (argc != 12) {
-    fprintf(stderr, "usage: %s SHELL N_INNER ROOT_REF MAX_LEAF_DEPTH STACK nodes spheres quads tris rays out\n", argv[0]);
+  const bool table_mode = argc == 13 && strcmp(argv[12], "table") == 0;
+  if (argc != 12 && !table_mode) {
+    fprintf(stderr, "usage: %s SHELL N_INNER ROOT_REF MAX_LEAF_DEPTH STACK nodes spheres quads tris rays out [table]\n",
+            argv[0]);
     return 2;
   }
   Scene sc;
@@ -200,6 +224,22 @@ int main(int argc, char** argv) {
     sph = f4(sc.spheres, 4 * ix);
   }
 
+  // the wave's table: each entry computed where it is read, or (table mode)
+  // built once into an array, lane by lane, as the megakernel's prologue does
+  const SphereLoad sl{&sc.spheres};
+  const ShellTableDirect<Load, SphereLoad> direct{ld, sl, ch, pl, sc.shell, sc.n_inner};
+  uint32_t tab[128];
+  for (int lane = 0; lane < 64; ++lane) {
+    tab[lane] = shell_table_entry(ld, sl, ch, pl, sc.shell, sc.n_inner, lane);
+    tab[64 + lane] = shell_table_entry(ld, sl, ch, pl, sc.shell, sc.n_inner, 64 + lane);
+  }
+  const TableLoad tl{tab};
+  if (table_mode) {
+    printf("table");
+    for (int i = 0; i < kTabSize; ++i) printf(" %08x", tab[i]);
+    printf("\n");
+  }
+
   const size_t n = rays.size() / 7;
   std::vector<uint32_t> out(8 * n);
   bool overflow = false;
@@ -218,21 +258,37 @@ int main(int argc, char** argv) {
     ray(w, o, d, q[6]);
     bool gate = false, expanded = false, finished = false;
     if (pl.m > 0) {
-      const pt_v3 oc = pt_sub(o, pt_v3f(sph.x, sph.y, sph.z));
-      gate = 4.0f * pt_dot(oc, oc) <= sph.w * sph.w;
+      const float4 gs = table_mode ? make_float4(pt_chain_f(tab[kTabSphere]), pt_chain_f(tab[kTabSphere + 1]),
+                                                 pt_chain_f(tab[kTabSphere + 2]), pt_chain_f(tab[kTabSphere + 3]))
+                                   : sph;
+      const pt_v3 oc = pt_sub(o, pt_v3f(gs.x, gs.y, gs.z));
+      gate = 4.0f * pt_dot(oc, oc) <= gs.w * gs.w;
     }
+    auto push = [&](uint32_t ref, float E) { w.push(ref, E); };
     if (gate)
-      expanded = shell_chain_begin(ld, ch, pl, w.o, w.d, w.inv, w.tmin, w.closest,
-                                   [&](uint32_t ref, float E) { w.push(ref, E); });
+      expanded = table_mode ? shell_chain_begin(tl, ch, pl, w.o, w.d, w.inv, w.tmin, w.closest, true, push)
+                            : shell_chain_begin(direct, ch, pl, w.o, w.d, w.inv, w.tmin, w.closest, true, push);
     if (!expanded) begin_root(sc, w);
     run(sc, w);
     if (pl.skip && gate && w.best == 0) {  // shell_hit: the leaf's box, then its sphere
       finished = true;
       float E, X, t;
-      slab6(w, pbox, pc, E, X);
-      if (pt_minf(X, kTMax) >= E && hit_sphere_t<true>(sph, w.o, w.d, w.tmin, kTMax, t)) {
-        w.closest = t;
-        w.best = (int32_t)pt_chain_u(pbox[12 + pc]);
+      if (table_mode) {  // shell_from_table: the leaf's box in the order lo x, y, z, hi x, y, z, its code and sphere
+        float b[12];
+        for (int a = 0; a < 6; ++a) b[2 * a] = b[2 * a + 1] = pt_chain_f(tab[kTabLeaf + a]);
+        slab6(w, b, 0, E, X);
+        const float4 ts = make_float4(pt_chain_f(tab[kTabSphere]), pt_chain_f(tab[kTabSphere + 1]),
+                                      pt_chain_f(tab[kTabSphere + 2]), pt_chain_f(tab[kTabSphere + 3]));
+        if (pt_minf(X, kTMax) >= E && hit_sphere_t<true>(ts, w.o, w.d, w.tmin, kTMax, t)) {
+          w.closest = t;
+          w.best = (int32_t)tab[kTabLeaf + 6];
+        }
+      } else {
+        slab6(w, pbox, pc, E, X);
+        if (pt_minf(X, kTMax) >= E && hit_sphere_t<true>(sph, w.o, w.d, w.tmin, kTMax, t)) {
+          w.closest = t;
+          w.best = (int32_t)pt_chain_u(pbox[12 + pc]);
+        }
       }
     }
     overflow = overflow || w.overflow;
