@@ -16,8 +16,8 @@ import numpy as np
 import torch
 
 from . import _lib, guide, motion, post, temporal, update, wf_tiles
-from .scene_data import (DeviceLayout, PRIM_QUAD, PRIM_SPHERE, PRIM_TRIANGLE, SceneArrays, camera_upload,
-                         fill_node_boxes, pack_device, shell_hint)
+from .scene_data import (BUILD_COLUMNS, DeviceLayout, PRIM_QUAD, PRIM_SPHERE, PRIM_TRIANGLE, SceneArrays, camera_upload,
+                         fill_node_boxes, pack_device, shell_hint, unpack_quads, unpack_tris)
 
 
 def _stream_ptr(stream=None, device=None):
@@ -192,9 +192,15 @@ class DeviceScene:
         (scene_data.find_shell on the mirror; 0 if the claim no longer holds).
         Topology, materials and counts do not change: for anything else build a
         new DeviceScene. ``flags`` as for update_call (same bits either way)."""
-        st = self._update_state()
-        sa, lay = self.arrays, self.layout
-        edits, ints, floats, lists, ni, nf = {}, [], [], {}, 0, 0
+        edits = self._check_edits(spheres, quads, triangles)
+        self._upload_edits(edits, stream, flags)
+        (stream if stream is not None else torch.cuda.current_stream(self.device)).synchronize()
+        self._refresh_mirror(edits)
+
+    def _check_edits(self, spheres, quads, triangles):
+        """update_primitives' arguments checked: {type code: (int64 indices, (n, row floats) rows, (n, build floats)
+        build records)} of the non-empty ones. Nothing is uploaded."""
+        st, edits = self._update_state(), {}
         for t, arg, name in ((PRIM_SPHERE, spheres, 'spheres'), (PRIM_QUAD, quads, 'quads'),
                              (PRIM_TRIANGLE, triangles, 'triangles')):
             if arg is None:
@@ -216,15 +222,20 @@ class DeviceScene:
             rows, build = rows.reshape(n, update.ROW_FLOATS[t]), build.reshape(n, update.BUILD_FLOATS[t])
             if not (np.isfinite(rows).all() and np.isfinite(build).all()):
                 raise ValueError(f'{name}: rows and build records must be finite')
-            same = {PRIM_SPHERE: (rows, build), PRIM_QUAD: (rows[:, 4:13], build),
-                    PRIM_TRIANGLE: (rows[:, 0:3], build[:, 0:3])}[t]
-            if same[0].tobytes() != same[1].tobytes():
+            points = rows[:, BUILD_COLUMNS[t]]
+            if points.tobytes() != build[:, :points.shape[1]].tobytes():
                 raise ValueError(f'{name}: a row and its build record name different points')
-            if n == 0:
-                continue
-            prim, leaf = st['dev_of'][t][idx], st['leaf_of'][t][idx]
-            edits[t] = (idx, rows, build, prim)
-            ints += [prim.astype(np.int32), leaf.astype(np.int32)]
+            if n:
+                edits[t] = (idx, rows, build)
+        return edits
+
+    def _upload_edits(self, edits, stream, flags):
+        """The checked edits to the device in one int and one float tensor, and update_call on them."""
+        st = self._update_state()
+        ints, floats, lists, ni, nf = [], [], {}, 0, 0
+        for t, (idx, rows, build) in edits.items():
+            n = idx.size
+            ints += [st['dev_of'][t][idx].astype(np.int32), st['leaf_of'][t][idx].astype(np.int32)]
             floats += [rows.reshape(-1), build.reshape(-1)]
             lists[t] = (ni, ni + n, nf, nf + rows.size, n)  # element offsets, made pointers below
             ni, nf = ni + 2 * n, nf + rows.size + build.size
@@ -234,29 +245,24 @@ class DeviceScene:
             pi, pf = ti.data_ptr(), tf.data_ptr()
             lists = {t: (pi + 4 * a, pi + 4 * b, pf + 4 * c, pf + 4 * d, n) for t, (a, b, c, d, n) in lists.items()}
         self.update_call(lists, stream, flags)
-        (stream if stream is not None else torch.cuda.current_stream(self.device)).synchronize()
-        # the mirror: the boxes from the device, the edited primitives from the arguments
+
+    def _refresh_mirror(self, edits):
+        """``arrays``, ``layout`` and the view after a finished update: the boxes
+        from the device, the edited primitives from the arguments."""
+        st, sa, lay = self._update_state(), self.arrays, self.layout
         nb = sa.num_bvh_nodes
         if nb:
             rn = self.t_ref_nodes.cpu().numpy().reshape(-1, 12)
             sa.bvh['bvh_bbox_min'][:] = rn[:nb, 0:3]
             sa.bvh['bvh_bbox_max'][:] = rn[:nb, 4:7]
-        for t, (idx, rows, build, prim) in edits.items():
+        for t, (idx, rows, build) in edits.items():
             if t == PRIM_SPHERE:
                 sa.sphere_data[idx] = rows
-                lay.spheres[prim] = rows
-            elif t == PRIM_QUAD:
-                for key, a, b in (('quad_normal', 0, 3), ('quad_Q', 4, 7), ('quad_u', 7, 10), ('quad_v', 10, 13),
-                                  ('quad_w', 13, 16)):
-                    sa.quads[key][idx] = rows[:, a:b]
-                sa.quads['quad_D'][idx] = rows[:, 3]
-                lay.quads[prim] = rows
             else:
-                for key, src, a in (('triangle_v0', build, 0), ('triangle_v1', build, 3), ('triangle_v2', build, 6),
-                                    ('triangle_edge1', rows, 3), ('triangle_edge2', rows, 6),
-                                    ('triangle_normal', rows, 9)):
-                    sa.tris[key][idx] = src[:, a:a + 3]
-                lay.tris[prim] = rows
+                mirror, new = (sa.quads, unpack_quads(rows)) if t == PRIM_QUAD else (sa.tris, unpack_tris(rows, build))
+                for key, values in new.items():
+                    mirror[key][idx] = values
+            (lay.spheres, lay.tris, lay.quads)[t][st['dev_of'][t][idx]] = rows  # by type code
         if nb:
             lay.ref_nodes[:] = rn[:nb]
             if st['inner'].size:
@@ -349,6 +355,16 @@ class Integrator:
     def _stream(self, stream):
         return _stream_ptr(stream, self.scene.device)
 
+    # the per-pixel buffers the host layer takes: the shape after (height, width), and the dtype
+    IMAGE_KINDS = {'accum': ((3,), torch.float32), 'stats': ((4,), torch.float32), 'out': ((3,), torch.float32),
+                   'guides': ((guide.GUIDE_CHANNELS,), torch.float32), 'ids': ((), torch.int32),
+                   'var': ((), torch.float32)}
+
+    def _check_image(self, kind, t, height, width):
+        """``t`` is a ``kind`` buffer of a height x width image on the scene's device (_check_tensor)."""
+        tail, dtype = self.IMAGE_KINDS[kind]
+        _check_tensor(kind, t, (height, width) + tail, dtype, self.scene.device)
+
     # multi-sample megakernel calls run as (tile, sample chunk) work units with
     # staged colours (ptmi_mk_render_ws); single samples accumulate directly
     MK_STAGED_MIN_SAMPLES = 2
@@ -357,7 +373,7 @@ class Integrator:
         """Megakernel render of samples [sample_begin, sample_begin + sample_count)
         added into accum in sample order. overlap=True: consecutive calls
         pipeline (see render_mk_overlapped)."""
-        _check_accum(accum, frame, self.scene.device)
+        self._check_image('accum', accum, frame.height, frame.width)
         if overlap:
             return self.render_mk_overlapped(frame, accum, sample_begin, sample_count, stream)
         if staged is None:
@@ -413,7 +429,6 @@ class Integrator:
           previous call: the scene must not change between overlapped calls,
           and work on the caller's stream after this call sees the resolved
           accumulator as usual."""
-        import torch
         dev = self.scene.device
         caller = stream if stream is not None else torch.cuda.current_stream(dev)
         npix = frame.w * len(frame_pixel_rows(frame))
@@ -481,14 +496,14 @@ class Integrator:
         return self._ws
 
     def render_wf(self, frame, accum, sample_begin, sample_count, stream=None):
-        _check_accum(accum, frame, self.scene.device)
+        self._check_image('accum', accum, frame.height, frame.width)
         with self._dev():
             ws = self.workspace(frame, sample_count)
             self._call('ptmi_wf_render', self.scene.view, frame, ws.data_ptr(), self._ws_bytes, accum.data_ptr(),
                        int(sample_begin), int(sample_count), self._cnt(), self._stream(stream))
 
     def clear(self, frame, accum, stream=None):
-        _check_accum(accum, frame, self.scene.device)
+        self._check_image('accum', accum, frame.height, frame.width)
         with self._dev():
             self._call('ptmi_clear', frame, accum.data_ptr(), self._stream(stream))
 
@@ -503,7 +518,7 @@ class Integrator:
         with self._dev():
             out = torch.empty((h, w, 3), dtype=torch.uint8, device=accum.device)
             if stats is not None:
-                _check_stats(stats, h, w, self.scene.device)
+                self._check_image('stats', stats, h, w)
                 self._call('ptmi_tonemap_stats', accum.data_ptr(), stats.data_ptr(), out.data_ptr(), w, h,
                            self._stream(stream))
                 return out
@@ -530,19 +545,9 @@ class Integrator:
                 'list': torch.arange(tx * ty, dtype=torch.int32, device=dev), 'n': tx * ty, 'grid': (tx, ty)}
 
     def clear_stats(self, frame, stats, stream=None):
-        _check_stats(stats, frame.height, frame.width, self.scene.device)
+        self._check_image('stats', stats, frame.height, frame.width)
         with self._dev():
             self._call('ptmi_stats_clear', frame, stats.data_ptr(), self._stream(stream))
-
-    def _check_tiles(self, tiles):
-        """(tensor or None, count) of a ``tiles`` argument: None, or (int32 device tensor of tile ids, count)."""
-        tl, nt = (None, 0) if tiles is None else tiles
-        if tl is not None:
-            nt = int(nt)
-            if not (isinstance(tl, torch.Tensor) and tl.dtype == torch.int32 and tl.is_contiguous()
-                    and tl.device == self.scene.device and 0 <= nt <= tl.numel()):
-                raise _lib.PtmiError('tiles must be (contiguous int32 tensor on the scene device, count <= its length)')
-        return tl, nt
 
     def render_mk_stats(self, frame, accum, stats, sample_begin, sample_count, tiles=None, stream=None):
         """Megakernel samples [sample_begin, sample_begin + sample_count) added
@@ -550,10 +555,10 @@ class Integrator:
         always the staged trace plus the stats resolve, single samples
         included. ``tiles``: None for the whole frame, or (int32 device tensor
         of tile ids, count): only those tiles are traced and resolved."""
-        _check_accum(accum, frame, self.scene.device)
-        _check_stats(stats, frame.height, frame.width, self.scene.device)
+        self._check_image('accum', accum, frame.height, frame.width)
+        self._check_image('stats', stats, frame.height, frame.width)
         sample_count = int(sample_count)
-        tl, nt = self._check_tiles(tiles)
+        tl, nt = _check_tiles(tiles, self.scene.device)
         npix = frame.w * len(frame_pixel_rows(frame))
         if npix == 0 or sample_count <= 0 or (tl is not None and nt == 0):
             return
@@ -578,9 +583,9 @@ class Integrator:
         the whole frame, or (int32 device tensor of tile ids, count): only
         those tiles are traced and resolved (ptmi_wf_render_tiles_stats,
         include/ptmi_wf_tiles.h); an empty list returns at once."""
-        _check_accum(accum, frame, self.scene.device)
-        _check_stats(stats, frame.height, frame.width, self.scene.device)
-        tl, nt = self._check_tiles(tiles)
+        self._check_image('accum', accum, frame.height, frame.width)
+        self._check_image('stats', stats, frame.height, frame.width)
+        tl, nt = _check_tiles(tiles, self.scene.device)
         if tl is not None and nt == 0:
             return
         with self._dev():
@@ -599,7 +604,7 @@ class Integrator:
         """Tile errors and states from stats (ptmi_tile_update) into the
         buffers of ``tiles`` (new_tiles); returns the number of active tiles
         (one 4-byte readback) and stores it as tiles['n']."""
-        _check_stats(stats, frame.height, frame.width, self.scene.device)
+        self._check_image('stats', stats, frame.height, frame.width)
         with self._dev():
             self._call('ptmi_tile_update', frame, stats.data_ptr(), float(threshold), int(min_spp), int(max_spp),
                        tiles['state'].data_ptr(), tiles['err'].data_ptr(), tiles['list'].data_ptr(),
@@ -611,12 +616,10 @@ class Integrator:
 
     # ------------------------------------------------ post-processing (ptmi.post)
     def _check_denoise_inputs(self, accum, stats):
-        dev = self.scene.device
-        if not (isinstance(accum, torch.Tensor) and accum.dtype == torch.float32 and accum.is_contiguous()
-                and accum.dim() == 3 and accum.shape[2] == 3 and accum.device == dev):
-            raise _lib.PtmiError(f'accum must be a contiguous float32 tensor of shape (H, W, 3) on {dev}')
+        """(height, width) of an (accum, stats) pair of one image, of any size."""
+        _check_tensor('accum', accum, ('H', 'W', 3), torch.float32, self.scene.device)
         h, w = int(accum.shape[0]), int(accum.shape[1])
-        _check_stats(stats, h, w, dev)
+        self._check_image('stats', stats, h, w)
         return h, w
 
     def _denoise_buffers(self, h, w, out, var):
@@ -627,10 +630,8 @@ class Integrator:
             out = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
         if var is None:
             var = torch.empty((h, w), dtype=torch.float32, device=dev)
-        for t, shape, name in ((out, (h, w, 3), 'out'), (var, (h, w), 'var')):
-            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.is_contiguous()
-                    and tuple(t.shape) == shape and t.device == dev):
-                raise _lib.PtmiError(f'{name} must be a contiguous float32 tensor of shape {shape} on {dev}')
+        self._check_image('out', out, h, w)
+        self._check_image('var', var, h, w)
         if self._dn_ws is None or self._dn_ws.numel() * 4 < need:
             self._dn_ws = None
             self._dn_ws = torch.empty(need // 4, dtype=torch.float32, device=dev)
@@ -651,22 +652,43 @@ class Integrator:
                                         var.data_ptr(), self._stream(stream)), 'ptmi_denoise')
         return out, var
 
-    # ------------------------------------------------ guides (ptmi.guide)
+    # ------------------------------------------------ guides (ptmi.guide, ptmi.motion)
     def trace_guides(self, frame, out=None, stream=None):
         """First-hit guide buffers of a whole, unbanded frame (ptmi_guide_trace,
         include/ptmi_guide.h): an (H, W, 8) f32 tensor {nx, ny, nz, depth, ar,
         ag, ab, hit} from one deterministic primary ray per pixel,
         asynchronous on ``stream``; ``out`` is used if given."""
-        lib = guide.load()
+        return self._trace_guides(frame, out, stream, False)[0]
+
+    def trace_guides_ids(self, frame, out=None, stream=None):
+        """``trace_guides`` that also returns which primitive each pixel sees
+        (ptmi_guide_trace_ids, include/ptmi_motion.h): ``(guides, ids)``, the
+        guides byte for byte ``trace_guides``', ids an (H, W) int32 tensor of
+        ``type << 28 | device primitive index`` on surface hits and -1
+        elsewhere. ``out``: a (guides, ids) pair to write into."""
+        return self._trace_guides(frame, out, stream, True)
+
+    def _trace_guides(self, frame, out, stream, with_ids):
+        """trace_guides and trace_guides_ids: ptmi_guide_trace, or with the id image ptmi_guide_trace_ids."""
+        lib = (motion if with_ids else guide).load()
         dev = self.scene.device
-        shape = (int(frame.height), int(frame.width), guide.GUIDE_CHANNELS)
+        h, w = int(frame.height), int(frame.width)
         with self._dev():
             if out is None:
-                out = torch.empty(shape, dtype=torch.float32, device=dev)
-            _check_guides(out, shape[0], shape[1], dev)
-            _lib.check(lib.ptmi_guide_trace(self.scene.view, frame, out.data_ptr(), self._stream(stream)),
-                       'ptmi_guide_trace')
-        return out
+                out = (torch.empty((h, w, guide.GUIDE_CHANNELS), dtype=torch.float32, device=dev),
+                       torch.empty((h, w), dtype=torch.int32, device=dev) if with_ids else None)
+            elif not with_ids:
+                out = (out, None)
+            guides, ids = out
+            self._check_image('guides', guides, h, w)
+            if with_ids:
+                self._check_image('ids', ids, h, w)
+                _lib.check(lib.ptmi_guide_trace_ids(self.scene.view, frame, guides.data_ptr(), ids.data_ptr(),
+                                                    self._stream(stream)), 'ptmi_guide_trace_ids')
+            else:
+                _lib.check(lib.ptmi_guide_trace(self.scene.view, frame, guides.data_ptr(), self._stream(stream)),
+                           'ptmi_guide_trace')
+        return guides, ids
 
     def denoise_guided(self, accum, stats, guides, iterations=5, sigma=4.0, sigma_z=0.1, sigma_a=0.2,
                        normal_power_log2=5, demodulate=True, out=None, var=None, stream=None):
@@ -676,9 +698,8 @@ class Integrator:
         (ptmi_denoise_guided, include/ptmi_guide.h). Same return values and
         the same cached workspace as ``denoise``."""
         lib = guide.load()
-        dev = self.scene.device
         h, w = self._check_denoise_inputs(accum, stats)
-        _check_guides(guides, h, w, dev)
+        self._check_image('guides', guides, h, w)
         prm = guide.params(iterations, sigma, sigma_z, sigma_a, normal_power_log2, demodulate)
         with self._dev():
             out, var, ws = self._denoise_buffers(h, w, out, var)
@@ -687,7 +708,7 @@ class Integrator:
                                                var.data_ptr(), self._stream(stream)), 'ptmi_denoise_guided')
         return out, var
 
-    # ------------------------------------------------ temporal reprojection (ptmi.temporal)
+    # ------------------------------------ temporal reprojection (ptmi.temporal, ptmi.motion)
     def reproject(self, cur_cam, prev_cam, guides_cur, guides_prev, accum, stats, *, max_history=32.0, sigma_z=0.1,
                   normal_min=0.9, sigma_a=0.2, out=None, stream=None):
         """The history ``accum``, ``stats`` of a stats render from ``prev_cam``
@@ -699,46 +720,8 @@ class Integrator:
         pixels without history are zero. The cameras are camera-upload dicts
         or ``_lib.Camera`` values. Returns (accum, stats) as new tensors, or
         the pair ``out`` if given; asynchronous on ``stream``."""
-        lib = temporal.load()
-        dev = self.scene.device
-        h, w = self._check_denoise_inputs(accum, stats)
-        _check_guides(guides_cur, h, w, dev)
-        _check_guides(guides_prev, h, w, dev)
-        cur, prev = temporal.camera(cur_cam), temporal.camera(prev_cam)
-        prm = temporal.params(max_history, sigma_z, normal_min, sigma_a)
-        with self._dev():
-            if out is None:
-                out = (torch.empty_like(accum), torch.empty_like(stats))
-            out_accum, out_stats = out
-            self._check_denoise_inputs(out_accum, out_stats)
-            if tuple(out_accum.shape) != tuple(accum.shape):
-                raise _lib.PtmiError(f'out must be an (accum, stats) pair of a {w} x {h} image')
-            _lib.check(lib.ptmi_reproject(C.byref(cur), C.byref(prev), guides_cur.data_ptr(), guides_prev.data_ptr(),
-                                          accum.data_ptr(), stats.data_ptr(), w, h, C.byref(prm),
-                                          out_accum.data_ptr(), out_stats.data_ptr(), self._stream(stream)),
-                       'ptmi_reproject')
-        return out_accum, out_stats
-
-    # ------------------------------------------------ motion-aware reprojection (ptmi.motion)
-    def trace_guides_ids(self, frame, out=None, stream=None):
-        """``trace_guides`` that also returns which primitive each pixel sees
-        (ptmi_guide_trace_ids, include/ptmi_motion.h): ``(guides, ids)``, the
-        guides byte for byte ``trace_guides``', ids an (H, W) int32 tensor of
-        ``type << 28 | device primitive index`` on surface hits and -1
-        elsewhere. ``out``: a (guides, ids) pair to write into."""
-        lib = motion.load()
-        dev = self.scene.device
-        h, w = int(frame.height), int(frame.width)
-        with self._dev():
-            if out is None:
-                out = (torch.empty((h, w, guide.GUIDE_CHANNELS), dtype=torch.float32, device=dev),
-                       torch.empty((h, w), dtype=torch.int32, device=dev))
-            guides, ids = out
-            _check_guides(guides, h, w, dev)
-            _check_ids(ids, h, w, dev)
-            _lib.check(lib.ptmi_guide_trace_ids(self.scene.view, frame, guides.data_ptr(), ids.data_ptr(),
-                                                self._stream(stream)), 'ptmi_guide_trace_ids')
-        return guides, ids
+        return self._reproject(cur_cam, prev_cam, guides_cur, guides_prev, accum, stats,
+                               (max_history, sigma_z, normal_min, sigma_a), out, stream)
 
     def reproject_moved(self, cur_cam, prev_cam, guides_cur, guides_prev, ids_cur, ids_prev, prev_rows, accum, stats, *,
                         max_history=32.0, sigma_z=0.1, normal_min=0.9, sigma_a=0.2, match_ids=True, out=None,
@@ -751,24 +734,29 @@ class Integrator:
         ``match_ids`` a tap must also show the same primitive. ``ids_cur`` and
         ``ids_prev`` are ``trace_guides_ids``' id images of the two frames.
         Everything else, the return value included, is ``reproject``'s."""
-        lib = motion.load()
-        dev = self.scene.device
+        return self._reproject(cur_cam, prev_cam, guides_cur, guides_prev, accum, stats,
+                               (max_history, sigma_z, normal_min, sigma_a), out, stream,
+                               (ids_cur, ids_prev, prev_rows, match_ids))
+
+    def _reproject(self, cur_cam, prev_cam, guides_cur, guides_prev, accum, stats, prm, out, stream, moved=None):
+        """reproject, or with ``moved`` = (ids_cur, ids_prev, prev_rows, match_ids) reproject_moved:
+        ptmi_reproject or ptmi_reproject_moved. ``prm``: (max_history, sigma_z, normal_min, sigma_a)."""
+        lib = (motion if moved else temporal).load()
         h, w = self._check_denoise_inputs(accum, stats)
-        _check_guides(guides_cur, h, w, dev)
-        _check_guides(guides_prev, h, w, dev)
-        _check_ids(ids_cur, h, w, dev)
-        _check_ids(ids_prev, h, w, dev)
-        rows = tuple(prev_rows)
-        if len(rows) != 3:
-            raise _lib.PtmiError('prev_rows must be (spheres, quads, tris)')
-        for t, mine, name in zip(rows, (self.scene.t_spheres, self.scene.t_quads, self.scene.t_tris),
-                                 ('spheres', 'quads', 'tris')):
-            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.is_contiguous()
-                    and t.device == dev and t.shape == mine.shape):
-                raise _lib.PtmiError(f'prev_rows: {name} must be a contiguous float32 tensor of {mine.numel()} values '
-                                     f'on {dev} (DeviceScene.primitive_rows())')
+        self._check_image('guides', guides_cur, h, w)
+        self._check_image('guides', guides_prev, h, w)
+        if moved:
+            ids_cur, ids_prev, prev_rows, match_ids = moved
+            self._check_image('ids', ids_cur, h, w)
+            self._check_image('ids', ids_prev, h, w)
+            rows = tuple(prev_rows)
+            if len(rows) != 3:
+                raise _lib.PtmiError('prev_rows must be (spheres, quads, tris)')
+            for t, mine, name in zip(rows, (self.scene.t_spheres, self.scene.t_quads, self.scene.t_tris),
+                                     ('spheres', 'quads', 'tris')):
+                _check_tensor(f'prev_rows: {name}', t, tuple(mine.shape), torch.float32, self.scene.device)
         cur, prev = temporal.camera(cur_cam), temporal.camera(prev_cam)
-        prm = motion.params(max_history, sigma_z, normal_min, sigma_a, match_ids)
+        prm = motion.params(*prm, match_ids) if moved else temporal.params(*prm)
         with self._dev():
             if out is None:
                 out = (torch.empty_like(accum), torch.empty_like(stats))
@@ -776,12 +764,15 @@ class Integrator:
             self._check_denoise_inputs(out_accum, out_stats)
             if tuple(out_accum.shape) != tuple(accum.shape):
                 raise _lib.PtmiError(f'out must be an (accum, stats) pair of a {w} x {h} image')
-            _lib.check(lib.ptmi_reproject_moved(C.byref(cur), C.byref(prev), guides_cur.data_ptr(),
-                                                guides_prev.data_ptr(), accum.data_ptr(), stats.data_ptr(),
-                                                ids_cur.data_ptr(), ids_prev.data_ptr(), self.scene.view,
-                                                rows[0].data_ptr(), rows[1].data_ptr(), rows[2].data_ptr(), w, h,
-                                                C.byref(prm), out_accum.data_ptr(), out_stats.data_ptr(),
-                                                self._stream(stream)), 'ptmi_reproject_moved')
+            head = (C.byref(cur), C.byref(prev), guides_cur.data_ptr(), guides_prev.data_ptr(), accum.data_ptr(),
+                    stats.data_ptr())
+            tail = (w, h, C.byref(prm), out_accum.data_ptr(), out_stats.data_ptr(), self._stream(stream))
+            if moved:
+                _lib.check(lib.ptmi_reproject_moved(*head, ids_cur.data_ptr(), ids_prev.data_ptr(), self.scene.view,
+                                                    rows[0].data_ptr(), rows[1].data_ptr(), rows[2].data_ptr(), *tail),
+                           'ptmi_reproject_moved')
+            else:
+                _lib.check(lib.ptmi_reproject(*head, *tail), 'ptmi_reproject')
         return out_accum, out_stats
 
     def _after_traces(self, stream):
@@ -826,35 +817,24 @@ class Integrator:
             self._reset_event = ev  # side streams created after this reset wait on it too
 
 
-def _check_stats(stats, height, width, device=None):
-    if not (isinstance(stats, torch.Tensor) and stats.is_cuda and stats.dtype == torch.float32
-            and stats.is_contiguous() and tuple(stats.shape) == (height, width, 4)):
-        raise _lib.PtmiError(f'stats must be a contiguous cuda float32 tensor of shape ({height}, {width}, 4)')
-    if device is not None and stats.device != device:
-        raise _lib.PtmiError(f'stats is on {stats.device}, the scene on {device}')
+def _check_tensor(name, t, shape, dtype, device):
+    """The host layer's one argument check: ``t`` is a contiguous cuda tensor of
+    ``dtype`` and ``shape`` on ``device``. A str in ``shape`` stands for any
+    size and names it in the message. Raises PtmiError."""
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous()
+            and t.dim() == len(shape) and all(isinstance(n, str) or n == m for n, m in zip(shape, t.shape))):
+        raise _lib.PtmiError(f'{name} must be a contiguous cuda {str(dtype).split(".")[-1]} tensor of shape '
+                             f'({", ".join(str(n) for n in shape)})')
+    if t.device != device:
+        raise _lib.PtmiError(f'{name} is on {t.device}, the scene on {device}')
 
 
-def _check_guides(guides, height, width, device=None):
-    shape = (height, width, guide.GUIDE_CHANNELS)
-    if not (isinstance(guides, torch.Tensor) and guides.is_cuda and guides.dtype == torch.float32
-            and guides.is_contiguous() and tuple(guides.shape) == shape):
-        raise _lib.PtmiError(f'guides must be a contiguous cuda float32 tensor of shape {shape}')
-    if device is not None and guides.device != device:
-        raise _lib.PtmiError(f'guides is on {guides.device}, the scene on {device}')
-
-
-def _check_ids(ids, height, width, device=None):
-    if not (isinstance(ids, torch.Tensor) and ids.is_cuda and ids.dtype == torch.int32 and ids.is_contiguous()
-            and tuple(ids.shape) == (height, width)):
-        raise _lib.PtmiError(f'ids must be a contiguous cuda int32 tensor of shape ({height}, {width})')
-    if device is not None and ids.device != device:
-        raise _lib.PtmiError(f'ids is on {ids.device}, the scene on {device}')
-
-
-def _check_accum(accum, frame, device=None):
-    if not (isinstance(accum, torch.Tensor) and accum.is_cuda and accum.dtype == torch.float32
-            and accum.is_contiguous() and tuple(accum.shape) == (frame.height, frame.width, 3)):
-        raise _lib.PtmiError(f'accum must be a contiguous cuda float32 tensor of shape '
-                             f'({frame.height}, {frame.width}, 3)')
-    if device is not None and accum.device != device:
-        raise _lib.PtmiError(f'accum is on {accum.device}, the scene on {device}')
+def _check_tiles(tiles, device):
+    """(tensor or None, count) of a ``tiles`` argument: None, or (int32 tensor of tile ids on ``device``, count)."""
+    tl, nt = (None, 0) if tiles is None else tiles
+    if tl is not None:
+        nt = int(nt)
+        _check_tensor('tiles', tl, ('N',), torch.int32, device)
+        if not 0 <= nt <= tl.numel():
+            raise _lib.PtmiError(f'tiles: the count must be in [0, {tl.numel()}], the length of the list')
+    return tl, nt

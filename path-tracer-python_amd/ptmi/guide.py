@@ -2,8 +2,8 @@
 buffers (normal, depth, albedo) and the a-trous denoiser guided by them.
 
 The entry points live in the same libptmi.so as the integrator's and are
-loaded through ``_lib.load()``; their signature table is kept here, apart from
-``_lib.SIGNATURES`` (include/ptmi.h) and ``post.SIGNATURES`` (include/ptmi_post.h).
+loaded through ``_lib.load()``; their signature table is kept here and bound by
+``_lib.bind``.
 """
 from __future__ import annotations
 

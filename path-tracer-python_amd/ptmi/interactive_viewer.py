@@ -31,7 +31,9 @@ import math
 import statistics
 import time
 
-from .renderer import MI355XRenderer
+import torch
+
+from .renderer import MI355XRenderer, _History
 
 
 def spherical_from(lookfrom, lookat):
@@ -71,15 +73,12 @@ class InteractiveViewer(MI355XRenderer):
         self.max_history = float(max_history)
         self.history_fraction = None  # pixels with history after the last reprojection
         self._sample_origin = 0  # RNG sample index of current_sample == 0: rises across restarts
-        self._history_cam = None  # camera and guides of the last render: what the rendered history was seen with
-        self._history_guides = None
-        # motion=True: update_primitives carries the history across the update
-        # (MI355XRenderer.reproject_history with prev_ids / prev_rows, DESIGN.md
-        # §18). The id image of the last render, and, once the scene has been
-        # updated since that render, the primitive rows it was rendered with.
+        # what the last render was seen with (renderer._History): its camera and
+        # guides. motion=True: update_primitives carries the history across the
+        # update, so also its id image, and, once the scene has
+        # been updated since that render, the primitive rows it was rendered with.
+        self._history = None
         self.motion = bool(motion)
-        self._history_ids = None
-        self._history_rows = None
         self._history_kept = False  # the last restart reprojected: the next render keeps accum / stats
         self.mouse_down = False
         self.last_mouse_x = 0
@@ -119,8 +118,8 @@ class InteractiveViewer(MI355XRenderer):
 
     def _restart_with_history(self, what='Camera rotated'):
         """The temporal restart: the rendered history reprojected to the
-        camera uploaded (and, in a motion viewer, the scene updated) since. _history_cam / _history_guides stay those of the
-        last camera samples were rendered at, so a further restart with no
+        camera uploaded (and, in a motion viewer, the scene updated) since.
+        _history stays that of the last camera samples were rendered at, so a further restart with no
         sample in between (the next step of one drag) reprojects that same
         rendered history again (reproject_history(again=True)) instead of
         resampling the reprojected one. current_sample restarts at 0 as the
@@ -131,10 +130,8 @@ class InteractiveViewer(MI355XRenderer):
         self.current_sample = 0
         self.sample_times = []
         self.render_start_time = time.time()
-        # the scene was updated since the history was rendered: the motion-aware form, by the rows it had then
-        moved = dict(prev_ids=self._history_ids, prev_rows=self._history_rows) if self._history_rows is not None else {}
-        self.history_fraction = self.reproject_history(self._history_cam, self._history_guides, again=again,
-                                                       max_history=self.max_history, **moved)
+        # (a history with rows, of a scene updated since it was rendered, takes the motion-aware form)
+        self.history_fraction = self._reproject_from(self._history, again, max_history=self.max_history)
         self._history_kept = True
         self.integrator.reset_counters()
         self.is_rendering_active = True
@@ -142,17 +139,12 @@ class InteractiveViewer(MI355XRenderer):
               f"pixels (at most {self.max_history:g} samples each)\n{'─' * 60}")
 
     def restart_rendering(self):
-        if self.temporal and self.stats is not None and self._history_guides is not None and \
+        if self.temporal and self.stats is not None and self._history is not None and \
                 (self.current_sample > 0 or self._history_kept):
             return self._restart_with_history()
         self._history_kept = False
-        self.current_sample = 0
-        self.sample_times = []
         self.render_start_time = time.time()
-        self.clear_accumulation_buffer()
-        if self.stats is not None:  # a render with target_error: error estimates and tile states start over too
-            self._adaptive_reset()
-        self.integrator.reset_counters()
+        self._restart_image()  # after a render with target_error, error estimates and tile states start over too
         self.is_rendering_active = True
         print(f"\n{'─' * 60}\nCamera rotated - restarting render from sample 0\n{'─' * 60}")
 
@@ -165,15 +157,14 @@ class InteractiveViewer(MI355XRenderer):
         by the rule of ``_restart_with_history``: a second update, or a camera
         move, with no sample in between reprojects the rendered history again,
         not the reprojected one."""
-        if self.motion and self.stats is not None and self._history_guides is not None and \
-                self._history_ids is not None and (self.current_sample > 0 or self._history_kept):
-            if self._history_rows is None:  # the scene still is what the history was rendered with
-                self._history_rows = self.dscene.primitive_rows()
+        if self.motion and self.stats is not None and self._history is not None and \
+                self._history.ids is not None and (self.current_sample > 0 or self._history_kept):
+            if self._history.rows is None:  # the scene still is what the history was rendered with
+                self._history.rows = self.dscene.primitive_rows()
             self._apply_update(spheres, quads, triangles)
             return self._restart_with_history('Scene updated')
         super().update_primitives(spheres, quads, triangles)
-        self._history_cam = self._history_guides = self._history_ids = self._history_rows = None
-        self._history_kept = False
+        self._history, self._history_kept = None, False
         self.history_fraction = None
         self.render_start_time = time.time()
         self.is_rendering_active = True
@@ -223,7 +214,6 @@ class InteractiveViewer(MI355XRenderer):
         once, and a call that follows a reprojecting restart keeps the
         history: sample index ``next_sample_index`` goes on where the last
         render stopped, and the image divides each pixel by its own count."""
-        import torch
         spp = int(self.cam.samples_per_pixel)
         print('\nInteractiveViewer')
         print(f'Resolution: {self.cam.img_width}x{self.cam.img_height} | Max Samples: {spp} | Depth: {self.max_depth}')
@@ -246,11 +236,7 @@ class InteractiveViewer(MI355XRenderer):
                 self._adaptive = None  # no pass schedule: not resumable as a render_adaptive() run
                 self._adaptive_reset()
         if self.temporal:  # the guides of this camera, traced once: what a later restart reprojects by
-            if self.motion:
-                self._history_guides, self._history_ids = self.guides_ids()
-            else:
-                self._history_guides = self.guides()
-            self._history_cam, self._history_rows = self.frame.cam, None
+            self._history = _History(self.frame.cam, *(self.guides_ids() if self.motion else (self.guides(),)))
             self._history_kept = False
         self.integrator.reset_counters()
         print(f'  Kernel Warmup: {(time.time() - t0) * 1000:6.2f}ms')

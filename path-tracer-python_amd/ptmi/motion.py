@@ -3,9 +3,8 @@ also writes which primitive each pixel sees, and the temporal reprojection that
 follows a surface point back across a scene update.
 
 The entry points live in the same libptmi.so as the integrator's and are loaded
-through ``_lib.load()``; their signature table is kept here, apart from
-``_lib.SIGNATURES`` (include/ptmi.h), ``post.SIGNATURES``, ``guide.SIGNATURES``,
-``temporal.SIGNATURES``, ``wf_tiles.SIGNATURES`` and ``update.SIGNATURES``.
+through ``_lib.load()``; their signature table is kept here and bound by
+``_lib.bind``.
 """
 from __future__ import annotations
 

@@ -2,8 +2,8 @@
 variance-guided a-trous denoiser on a stats render's error estimates.
 
 The entry points live in the same libptmi.so as the integrator's and are
-loaded through ``_lib.load()``; their signature table is kept here, apart from
-``_lib.SIGNATURES`` (the exports of include/ptmi.h).
+loaded through ``_lib.load()``; their signature table is kept here and bound by
+``_lib.bind``.
 """
 from __future__ import annotations
 

@@ -51,10 +51,12 @@ the objects by the indices it takes. The image starts over.
 """
 from __future__ import annotations
 
+import dataclasses
 import os
 import time
 
 import numpy as np
+import torch
 
 from . import _lib, bvh as bvh_mod, core, device, scene_compiler
 from .scene_data import SceneArrays
@@ -64,6 +66,18 @@ from .scene_data import SceneArrays
 # Read when a renderer uploads its camera; the per-renderer attribute
 # `use_stackless_traversal` overrides it.
 USE_STACKLESS_TRAVERSAL = False
+
+
+@dataclasses.dataclass
+class _History:
+    """What a rendered history was seen with: the camera (a camera-upload dict
+    or ptmi_camera) and the guides of its frame and, for a scene updated since,
+    the id image of that frame (``guides_ids()``) and the primitive rows of its
+    scene (``DeviceScene.primitive_rows()``). One render, one scene revision."""
+    camera: object
+    guides: object
+    ids: object = None
+    rows: object = None
 
 
 class MI355XRenderer:
@@ -88,6 +102,7 @@ class MI355XRenderer:
         self.checkpoint_path = None
         self.checkpoint_every = 1
         self._resume_state = None
+        self._resume_tiles = None  # load_checkpoint(): the tile buffers of an adaptive render's checkpoint
         # adaptive sampling (render_adaptive): per-pixel stats, tile buffers, parameters, per-pass log
         self.stats = None
         self._tiles = None
@@ -97,13 +112,10 @@ class MI355XRenderer:
         self.denoised = None
         self.denoised_var = None
         self.denoise_seconds = None
-        # guides(): the guide image of the camera it was traced for, and the seconds the trace took
-        self._guides = None
-        self._guides_key = None
+        # guides() / guides_ids(): (_guide_key() they were traced for, guide image, id image or None), and the
+        # seconds the trace took
+        self._guide_cache = (None, None, None)
         self.guide_trace_seconds = None
-        # guides_ids(): the id image that goes with the guides, under the same key
-        self._ids = None
-        self._ids_key = None
         # reproject_history(): the (accum, stats) pair it writes into next, swapped with the live pair on each call
         self._history_spare = None
         # update_primitives(): bumped on every scene update; part of the guides' cache key
@@ -129,7 +141,6 @@ class MI355XRenderer:
                                                 images)
         self.dscene = device.DeviceScene.from_arrays(self.arrays, device_id)
         self.integrator = device.Integrator(self.dscene)
-        import torch
         self.accum = torch.zeros((self.cam.img_height, self.cam.img_width, 3), dtype=torch.float32,
                                  device=self.dscene.device)
         self._upload_camera()
@@ -143,7 +154,6 @@ class MI355XRenderer:
         self.frame = device.make_frame(self.cam, self.background_color, self.max_depth, self.seed, W, H,
                                        traversal='stackless' if self.use_stackless_traversal else 'stack')
         if tuple(self.accum.shape[:2]) != (H, W):
-            import torch
             self.accum = torch.zeros((H, W, 3), dtype=torch.float32, device=self.dscene.device)
 
     def _upload_camera_to_gpu(self):
@@ -167,25 +177,45 @@ class MI355XRenderer:
         self._integrator_label = 'megakernel'
         self.integrator.render_mk(self.frame, self.accum, int(sample), 1)
 
+    def _drop_denoised(self):
+        self.denoised = self.denoised_var = self.denoise_seconds = None
+
+    def _restart_image(self, adaptive=None):
+        """The image starts over: the sample count and times, the accumulator,
+        the counters and, with ``adaptive`` (by default: if there are stats),
+        the error estimates, the tile states and ``denoised``."""
+        self.current_sample = 0
+        self.sample_times = []
+        self.clear_accumulation_buffer()
+        if adaptive or (adaptive is None and self.stats is not None):
+            self._adaptive_reset()
+        self.integrator.reset_counters()
+
+    def _begin_render(self, warm_up, resume, what, adaptive):
+        """The prologue of a render: the state of a loaded checkpoint checked
+        and kept (``resume``), or one warm-up sample rendered and the image
+        started over (renderer.py:381-385); the counters reset either way."""
+        t0 = time.time()
+        if resume:
+            if self._resume_state is None:
+                raise ValueError(f'{what}(resume=True) needs load_checkpoint() first')
+            self._check_resume_state()
+            self.integrator.reset_counters()
+        else:
+            warm_up(self.frame, self.accum, 0, 1)
+            torch.cuda.synchronize(self.dscene.device)
+            times = self.sample_times
+            self._restart_image(adaptive)
+            self.sample_times = times  # like the reference's, a render adds to the times of the renders before it
+        self._resume_state = None
+        torch.cuda.synchronize(self.dscene.device)
+        self.timing['kernel_warmup'] = time.time() - t0
+
     def _run(self, render_fn, label, resume=False):
-        import torch
         self._integrator_label = label
         self._upload_camera()
         spp = int(self.cam.samples_per_pixel)
-        t0 = time.time()
-        if resume:  # continue a loaded checkpoint: no warm-up, keep the accumulator
-            if self._resume_state is None:
-                raise ValueError('render(resume=True) needs load_checkpoint() first')
-            self._check_resume_state()
-        else:
-            render_fn(self.frame, self.accum, 0, 1)  # warm-up sample, then cleared (renderer.py:381-385)
-            torch.cuda.synchronize(self.dscene.device)
-            self.clear_accumulation_buffer()
-            self.current_sample = 0
-        self._resume_state = None
-        self.integrator.reset_counters()
-        torch.cuda.synchronize(self.dscene.device)
-        self.timing['kernel_warmup'] = time.time() - t0
+        self._begin_render(render_fn, resume, 'render', adaptive=False)
         print(f'\n{self.__class__.__name__} ({label})')
         print(f'Resolution: {self.cam.img_width}x{self.cam.img_height} | Samples: {spp} | Depth: {self.max_depth}')
         print(f'Spheres: {self.num_spheres} | BVH Nodes: {self.num_bvh_nodes}')
@@ -227,7 +257,7 @@ class MI355XRenderer:
         else:
             self.integrator.clear_stats(self.frame, self.stats)
         self._tiles = self.integrator.new_tiles(self.frame)
-        self.denoised = self.denoised_var = self.denoise_seconds = None  # of the render this one replaces
+        self._drop_denoised()  # of the render this one replaces
 
     def render_adaptive(self, target_error, pass_spp=None, min_spp=16, max_spp=None, integrator='megakernel',
                         resume=False, enable_preview: bool = True, tiles=None):
@@ -248,7 +278,6 @@ class MI355XRenderer:
         megakernel always lists, so tiles=False with it is a ValueError.
         Single device only (band_stride == 1). The image divides each pixel by
         its own sample count. resume=True continues a load_checkpoint() state bit-identically."""
-        import torch
         if integrator not in ('megakernel', 'wavefront'):
             raise ValueError(f'unknown integrator {integrator!r}')
         mk = integrator == 'megakernel'
@@ -269,22 +298,9 @@ class MI355XRenderer:
         self._adaptive = {'target_error': target_error, 'pass_spp': pass_spp, 'min_spp': min_spp, 'max_spp': max_spp,
                           'listed': listed}
         integ = self.integrator
-        t0 = time.time()
-        if resume:
-            if self._resume_state is None:
-                raise ValueError('render_adaptive(resume=True) needs load_checkpoint() first')
-            self._check_resume_state()
-        else:
-            (integ.render_mk if mk else integ.render_wf)(self.frame, self.accum, 0, 1)  # warm-up sample, then cleared
-            torch.cuda.synchronize(self.dscene.device)
-            self.clear_accumulation_buffer()
-            self._adaptive_reset()
-            self.current_sample = 0
+        self._begin_render(integ.render_mk if mk else integ.render_wf, resume, 'render_adaptive', adaptive=True)
+        if not resume:
             self.adaptive_passes = []
-        self._resume_state = None
-        integ.reset_counters()
-        torch.cuda.synchronize(self.dscene.device)
-        self.timing['kernel_warmup'] = time.time() - t0
         tiles = self._tiles
         ntiles = tiles['grid'][0] * tiles['grid'][1]
         print(f'\n{self.__class__.__name__} (adaptive {integrator})')
@@ -338,15 +354,19 @@ class MI355XRenderer:
         depth, ar, ag, ab, hit}. Traced once per camera and scene and cached;
         one deterministic primary ray per pixel, independent of the samples
         rendered."""
-        key = self._guide_key()
-        if self._guides is None or self._guides_key != key:
-            import torch
+        key, guides, _ = self._cached_guides()
+        if guides is None:
             t0 = time.time()
-            self._guides = self.integrator.trace_guides(self.frame)
+            guides = self.integrator.trace_guides(self.frame)
             torch.cuda.synchronize(self.integrator.scene.device)
             self.guide_trace_seconds = time.time() - t0
-            self._guides_key = key
-        return self._guides
+            self._guide_cache = (key, guides, None)
+        return guides
+
+    def _cached_guides(self):
+        """The cache entry (key, guides, ids) if it is of the current camera and scene, else (key, None, None)."""
+        key = self._guide_key()
+        return self._guide_cache if self._guide_cache[0] == key else (key, None, None)
 
     def guides_ids(self):
         """``(guides, ids)`` of the current camera (Integrator.trace_guides_ids,
@@ -355,21 +375,18 @@ class MI355XRenderer:
         | device primitive index``, -1 where no surface shows). Traced once per
         camera and scene and cached like ``guides()``, whose tensor it fills
         or reuses."""
-        key = self._guide_key()
-        if self._ids is None or self._ids_key != key:
-            import torch
-            have = self._guides if self._guides is not None and self._guides_key == key else None
+        key, have, ids = self._cached_guides()
+        if ids is None:
             ids = torch.empty((int(self.frame.height), int(self.frame.width)), dtype=torch.int32,
                               device=self.integrator.scene.device)
             t0 = time.time()
             out = (have if have is not None else torch.empty(tuple(ids.shape) + (8,), dtype=torch.float32,
                                                              device=ids.device), ids)
-            self._guides, self._ids = self.integrator.trace_guides_ids(self.frame, out=out)
+            self._guide_cache = (key,) + self.integrator.trace_guides_ids(self.frame, out=out)
             torch.cuda.synchronize(self.integrator.scene.device)
             if have is None:
                 self.guide_trace_seconds = time.time() - t0
-            self._guides_key = self._ids_key = key
-        return self._guides, self._ids
+        return self._guide_cache[1:]
 
     def guide_maps(self):
         """The guides as numpy AOVs: {'normal': (H, W, 3), 'depth': (H, W),
@@ -416,24 +433,16 @@ class MI355XRenderer:
         if keep_history:
             if self.stats is None:
                 raise ValueError('keep_history=True needs stats: render through the stats path (render_adaptive) first')
-            prev_cam = self.frame.cam
-            prev_guides, prev_ids = self.guides_ids()
-            prev_rows = self.dscene.primitive_rows()
+            history = _History(self.frame.cam, *self.guides_ids(), self.dscene.primitive_rows())
         elif params:
             raise ValueError(f'{sorted(params)} are reprojection parameters: they need keep_history=True')
         self._apply_update(spheres, quads, triangles)
         if keep_history:
-            return self.reproject_history(prev_cam, prev_guides, prev_ids=prev_ids, prev_rows=prev_rows, **params)
-        self.clear_accumulation_buffer()
-        self.current_sample = 0
-        self.sample_times = []
+            return self._reproject_from(history, **params)
+        self._restart_image()
         self.adaptive_passes = []
-        if self.stats is not None:
-            self._adaptive_reset()
-        self.denoised = self.denoised_var = self.denoise_seconds = None
         self._history_spare = None
-        self._guides = None
-        self.integrator.reset_counters()
+        self._guide_cache = (None, None, None)
 
     def _apply_update(self, spheres, quads, triangles):
         """update_primitives' checks and the update itself, up to the bumped
@@ -460,7 +469,6 @@ class MI355XRenderer:
                                                   for name in ('spheres', 'quads', 'triangles')))
         args = [(np.asarray(order[name], np.int64), rows, build) if order[name] else None
                 for name, (rows, build) in zip(('spheres', 'quads', 'triangles'), records)]
-        import torch
         torch.cuda.synchronize(self.dscene.device)  # no render of the scene in flight on any stream (overlapped traces)
         self.dscene.update_primitives(*args)
         for name, new in given.items():
@@ -499,33 +507,38 @@ class MI355XRenderer:
         if (prev_ids is None) != (prev_rows is None):
             raise ValueError('prev_ids and prev_rows go together: the id image and the primitive rows of the '
                              'history\'s frame')
-        import torch
-        if prev_ids is None:
+        return self._reproject_from(_History(prev_camera, prev_guides, prev_ids, prev_rows), again, match_ids,
+                                    **params)
+
+    def _reproject_from(self, history, again=False, match_ids=True, **params):
+        """reproject_history from the history's camera, guides and, if it has rows, ids and rows."""
+        cam, integ = self.frame.cam, self.integrator
+        if history.rows is None:
             guides = self.guides()
-            reproject = self.integrator.reproject
+
+            def reproject(accum, stats, out):
+                return integ.reproject(cam, history.camera, guides, history.guides, accum, stats, out=out, **params)
         else:
             guides, ids = self.guides_ids()
 
-            def reproject(cur, prev, g_cur, g_prev, accum, stats, **kw):
-                return self.integrator.reproject_moved(cur, prev, g_cur, g_prev, ids, prev_ids, prev_rows, accum,
-                                                       stats, match_ids=match_ids, **kw)
+            def reproject(accum, stats, out):
+                return integ.reproject_moved(cam, history.camera, guides, history.guides, ids, history.ids,
+                                             history.rows, accum, stats, match_ids=match_ids, out=out, **params)
         spare = self._history_spare
         if spare is not None and tuple(spare[0].shape) != tuple(self.accum.shape):
             spare = None
         if again:
             if spare is None:
                 raise ValueError('again=True needs an earlier reproject_history() of this image size')
-            reproject(self.frame.cam, prev_camera, guides, prev_guides, spare[0], spare[1],
-                      out=(self.accum, self.stats), **params)
+            reproject(spare[0], spare[1], (self.accum, self.stats))
         else:
             if spare is None:
                 spare = (torch.empty_like(self.accum), torch.empty_like(self.stats))
-            out = reproject(self.frame.cam, prev_camera, guides, prev_guides, self.accum, self.stats, out=spare,
-                            **params)
+            out = reproject(self.accum, self.stats, spare)
             self._history_spare = (self.accum, self.stats)
             self.accum, self.stats = out
         self._tiles = self.integrator.new_tiles(self.frame)
-        self.denoised = self.denoised_var = self.denoise_seconds = None
+        self._drop_denoised()
         return int((self.stats[..., 0] > 0).sum().item()) / (self.stats.shape[0] * self.stats.shape[1])
 
     def denoise(self, iterations=5, sigma=4.0, guided=False, **guided_params):
@@ -546,7 +559,6 @@ class MI355XRenderer:
             raise ValueError('no stats: render through render_adaptive')
         if guided_params and not guided:
             raise ValueError(f'{sorted(guided_params)} need guided=True')
-        import torch
         guides = self.guides() if guided else None  # (its own time is guide_trace_seconds)
         t0 = time.time()
         if guided:
@@ -587,9 +599,7 @@ class MI355XRenderer:
         to exactly ``path`` (no suffix added). The file is written next to it
         under a temporary name and renamed over it, so a crash mid-save leaves
         the previous checkpoint intact."""
-        import os
         import tempfile
-        import torch
         torch.cuda.synchronize(self.dscene.device)
         st = self._render_state()
         acc = self.accum.cpu().numpy()
@@ -619,7 +629,6 @@ class MI355XRenderer:
         render state (scene arrays, camera, seed, max_depth, background,
         traversal) is checked when the render resumes, after the
         render-time attributes have been applied."""
-        import torch
         with np.load(path, allow_pickle=False) as z:
             missing = [k for k in self._STATE_KEYS if k not in z.files]
             if missing:

@@ -392,26 +392,42 @@ def find_shell(sa: SceneArrays, max_leaf_depth: int):
     return best
 
 
+# f32 columns of a device row (include/ptmi.h) per reference-layout array: the one table of both directions
+QUAD_COLUMNS = {'quad_normal': slice(0, 3), 'quad_D': 3, 'quad_Q': slice(4, 7), 'quad_u': slice(7, 10),
+                'quad_v': slice(10, 13), 'quad_w': slice(13, 16)}
+TRI_COLUMNS = {'triangle_v0': slice(0, 3), 'triangle_edge1': slice(3, 6), 'triangle_edge2': slice(6, 9),
+               'triangle_normal': slice(9, 12)}
+# by primitive type code: the row columns that a builder-form record ({c, r}; {v0, v1, v2}; {Q, u, v}) begins with
+BUILD_COLUMNS = (slice(0, 4), TRI_COLUMNS['triangle_v0'], slice(4, 13))
+
+
+def _pack_rows(arrays, columns, width):
+    rows = np.zeros((arrays[next(iter(columns))].shape[0], width), np.float32)
+    for key, cols in columns.items():
+        rows[:, cols] = arrays[key]
+    return rows
+
+
 def pack_quads(q):
     """Device rows (include/ptmi.h: 16 f32) of reference-layout quad arrays (QUAD_KEYS), in their order."""
-    quads = np.zeros((q['quad_Q'].shape[0], 16), np.float32)
-    quads[:, 0:3] = q['quad_normal']
-    quads[:, 3] = q['quad_D']
-    quads[:, 4:7] = q['quad_Q']
-    quads[:, 7:10] = q['quad_u']
-    quads[:, 10:13] = q['quad_v']
-    quads[:, 13:16] = q['quad_w']
-    return quads
+    return _pack_rows(q, QUAD_COLUMNS, 16)
 
 
 def pack_tris(t):
     """Device rows (12 f32) of reference-layout triangle arrays (TRI_KEYS), in their order."""
-    tris = np.zeros((t['triangle_v0'].shape[0], 12), np.float32)
-    tris[:, 0:3] = t['triangle_v0']
-    tris[:, 3:6] = t['triangle_edge1']
-    tris[:, 6:9] = t['triangle_edge2']
-    tris[:, 9:12] = t['triangle_normal']
-    return tris
+    return _pack_rows(t, TRI_COLUMNS, 12)
+
+
+def unpack_quads(rows):
+    """pack_quads' inverse: the reference-layout arrays (QUAD_KEYS) of (n, 16) device rows."""
+    return {key: rows[:, cols] for key, cols in QUAD_COLUMNS.items()}
+
+
+def unpack_tris(rows, build):
+    """pack_tris' inverse: the reference-layout arrays (TRI_KEYS) of (n, 12) device
+    rows and their (n, 9) builder-form records {v0, v1, v2}; a row holds edges, not v1 and v2."""
+    return dict({key: rows[:, cols] for key, cols in TRI_COLUMNS.items()},
+                triangle_v1=build[:, 3:6], triangle_v2=build[:, 6:9])
 
 
 def fill_node_boxes(nodes, rows, bmin, bmax, l, r):

@@ -3,9 +3,8 @@ a stats render's history (accum and stats) from the previous camera to the
 current one by the guide images of both.
 
 The entry point lives in the same libptmi.so as the integrator's and is loaded
-through ``_lib.load()``; its signature table is kept here, apart from
-``_lib.SIGNATURES`` (include/ptmi.h), ``post.SIGNATURES`` (include/ptmi_post.h)
-and ``guide.SIGNATURES`` (include/ptmi_guide.h).
+through ``_lib.load()``; its signature table is kept here and bound by
+``_lib.bind``.
 """
 from __future__ import annotations
 

@@ -2,9 +2,8 @@
 a resident scene moved in place and its BVH refitted on the device.
 
 The entry point lives in the same libptmi.so as the integrator's and is loaded
-through ``_lib.load()``; its signature table is kept here, apart from
-``_lib.SIGNATURES`` (include/ptmi.h), ``post.SIGNATURES``, ``guide.SIGNATURES``,
-``temporal.SIGNATURES`` and ``wf_tiles.SIGNATURES``.
+through ``_lib.load()``; its signature table is kept here and bound by
+``_lib.bind``.
 
 ``topology`` builds what the call needs once per scene from the reference-layout
 BVH arrays; ``DeviceScene.update_primitives`` (ptmi.device) is the caller.

@@ -2,9 +2,8 @@
 the wavefront stats render restricted to a list of the frame's 64-pixel tiles.
 
 The entry point lives in the same libptmi.so as the integrator's and is loaded
-through ``_lib.load()``; its signature table is kept here, apart from
-``_lib.SIGNATURES`` (include/ptmi.h), ``post.SIGNATURES``, ``guide.SIGNATURES``
-and ``temporal.SIGNATURES``.
+through ``_lib.load()``; its signature table is kept here and bound by
+``_lib.bind``.
 """
 from __future__ import annotations
 

@@ -218,6 +218,13 @@ def test_listed_trace(integs):
                                               C.c_void_p(stats.data_ptr()), C.c_void_p(dev_list.data_ptr()), 0, 4,
                                               None) == 0
     assert eq(host(acc), acc_ref) and eq(host(stats), st_ref) and integ.read_counters()['paths'] == 0
+    # a list that is no contiguous 1-D int32 tensor on the device, and a count outside the list, are rejected
+    from ptmi import _lib
+    for bad in ((dev_list, dev_list.numel() + 1), (dev_list, -1), (dev_list.cpu(), 1), (dev_list.float(), 1),
+                (dev_list[::2], 1), (dev_list.view(5, 5), 1), (dev_list.tolist(), 1)):
+        with pytest.raises(_lib.PtmiError, match='^tiles'):
+            integ.render_mk_stats(fr, acc, stats, 0, 4, tiles=bad)
+    assert eq(host(acc), acc_ref) and eq(host(stats), st_ref) and integ.read_counters()['paths'] == 0
     integ.render_mk_stats(fr, acc, stats, 0, 4, tiles=(dev_list, dev_list.numel()))
     ah.accumulate(acc_ref, st_ref, cols, listed)
     g, s = host(acc), host(stats)

@@ -119,6 +119,17 @@ def test_out_var_may_be_null_and_outputs_may_be_given(integ):
     r = integ.denoise(a, s, 5, 4.0, out=out, var=var)
     assert r[0] is out and r[1] is var
     assert eq(host(out), ref_rgb) and eq(host(var), ref_var)
+    # outputs of another shape, dtype, layout or device are rejected before the call
+    from ptmi import _lib
+    for bad in (torch.zeros((11, 13, 4), device='cuda'), out.double(), out.cpu(),
+                torch.zeros((11, 13, 6), device='cuda')[..., ::2], host(out)):
+        with pytest.raises(_lib.PtmiError, match='out must be'):
+            integ.denoise(a, s, 5, 4.0, out=bad, var=var)
+    for bad in (torch.zeros((13, 11), device='cuda'), var.int(), var.cpu(),
+                torch.zeros((11, 26), device='cuda')[:, ::2]):
+        with pytest.raises(_lib.PtmiError, match='var must be'):
+            integ.denoise(a, s, 5, 4.0, out=out, var=bad)
+    assert eq(host(out), ref_rgb) and eq(host(var), ref_var)
     # the C call with out_var = NULL
     lib = post.load()
     need = post.workspace_bytes(13, 11)

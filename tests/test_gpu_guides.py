@@ -83,6 +83,15 @@ def test_trace_guides_into_a_given_tensor_on_a_side_stream():
         integ.trace_guides(device.make_frame(cam, bg, 50, 0, W, H, (0, 0, W, H - 1)))
     with pytest.raises(_lib.PtmiError, match='guides must be'):
         integ.trace_guides(fr, out=torch.zeros((H, W, 4), dtype=torch.float32, device='cuda'))
+    # the id form: the same check of the guides, and the id image's own
+    ids = torch.zeros((H, W), dtype=torch.int32, device='cuda')
+    with pytest.raises(_lib.PtmiError, match='guides must be'):
+        integ.trace_guides_ids(fr, out=(torch.zeros((H, W, 4), dtype=torch.float32, device='cuda'), ids))
+    for bad in (ids.float(), ids.cpu(), torch.zeros((H, W + 1), dtype=torch.int32, device='cuda')[:, :W],
+                torch.zeros((H, W, 1), dtype=torch.int32, device='cuda'), None):
+        with pytest.raises(_lib.PtmiError, match='ids must be'):
+            integ.trace_guides_ids(fr, out=(out, bad))
+    assert eq(out.cpu().numpy(), ref) and not ids.any()  # rejected before the call
 
 
 # ---------------------------------------------------------------- the guided filter

@@ -141,6 +141,27 @@ def test_reproject_moved_on_the_unmoved_scene_is_reproject():
     pa, ps = integ.reproject(case['cur'], case['prev'], dev(case['guides_cur']), dev(case['guides_prev']),
                              dev(case['accum']), dev(case['stats']))
     assert host(pa).tobytes() == a.tobytes() and host(ps).tobytes() == s.tobytes()  # flags 0: byte for byte
+    # what reproject_moved adds to reproject's arguments is checked like them, before the call
+    import torch
+    from ptmi import _lib
+    t = {k: dev(case[k]) for k in ('guides_cur', 'guides_prev', 'ids_cur', 'ids_prev', 'accum', 'stats')}
+    out = torch.full((H, W, 3), -1.0, device='cuda'), torch.full((H, W, 4), -1.0, device='cuda')
+
+    def rejected(match, rows=prev_rows, **bad):
+        v = dict(t, **bad)
+        with pytest.raises(_lib.PtmiError, match=match):
+            integ.reproject_moved(case['cur'], case['prev'], v['guides_cur'], v['guides_prev'], v['ids_cur'],
+                                  v['ids_prev'], rows, v['accum'], v['stats'], out=out)
+
+    rejected('ids must be', ids_cur=t['ids_cur'].float())
+    rejected('ids must be', ids_prev=t['ids_prev'].cpu())
+    rejected('ids must be', ids_cur=t['ids_cur'][:, :W - 1])
+    rejected('guides must be', guides_prev=t['stats'])
+    rejected(r'prev_rows must be \(spheres, quads, tris\)', rows=prev_rows[:2])
+    rejected('prev_rows: spheres must be', rows=(prev_rows[0][:-4], prev_rows[1], prev_rows[2]))
+    rejected('prev_rows: quads must be', rows=(prev_rows[0], prev_rows[1].double(), prev_rows[2]))
+    rejected('prev_rows: tris must be', rows=(prev_rows[0], prev_rows[1], prev_rows[2].cpu()))
+    assert (host(out[0]) == -1).all() and (host(out[1]) == -1).all()
 
 
 def test_a_sliding_sphere_takes_its_history_along_on_the_device():
@@ -388,7 +409,7 @@ def test_motion_viewer_keeps_its_history_across_updates(tmp_path):
     assert v.next_sample_index == 2 * spp
     counts = v.sample_count_map()
     assert counts.min() == spp and spp < counts.max() <= 8 + spp
-    assert v._history_rows is None  # the new render is the history, of the scene as it is
+    assert v._history.rows is None  # the new render is the history, of the scene as it is
 
 
 def test_viewer_without_motion_drops_its_history(tmp_path):
@@ -396,5 +417,5 @@ def test_viewer_without_motion_drops_its_history(tmp_path):
     assert v.motion is False
     v.render_interactive()
     v.update_primitives(spheres={1: _sphere_at(v, mh.SLIDE_TO)})
-    assert v.history_fraction is None and not host(v.accum).any() and v._history_guides is None
+    assert v.history_fraction is None and not host(v.accum).any() and v._history is None
     assert v.current_sample == 0

@@ -380,13 +380,14 @@ def test_renderer_update_resets_the_image_and_keeps_the_mirror(tmp_path):
     import torch
     from ptmi import core
     from ptmi.interactive_viewer import InteractiveViewer
+    from ptmi.renderer import _History
     random.seed(99)
     r = InteractiveViewer(_world((0, 0, -1)), _camera(), str(tmp_path / 'u.png'), temporal=True)
     tables = r.arrays.perlin
     r.render_adaptive(target_error=0.0, min_spp=4, max_spp=4)
     g0 = r.guides().cpu().numpy().copy()
     r.denoise()
-    r._history_cam, r._history_guides, r._history_kept = r.frame.cam, r.guides(), True
+    r._history, r._history_kept = _History(r.frame.cam, r.guides()), True
     r._history_spare = (torch.empty_like(r.accum), torch.empty_like(r.stats))
     assert r.current_sample == 4 and float(r.accum.abs().sum()) > 0 and r._tiles['n'] == 0
     moved = core.Sphere.stationary(core.vec3(-0.6, 0.3, -0.4), 0.35, r.primitives['spheres'][1].material)
@@ -397,7 +398,7 @@ def test_renderer_update_resets_the_image_and_keeps_the_mirror(tmp_path):
     ntiles = r._tiles['grid'][0] * r._tiles['grid'][1]
     assert r._tiles['n'] == ntiles and int(r._tiles['state'].sum()) == ntiles
     assert r.denoised is None and r.denoised_var is None and r._history_spare is None
-    assert r._history_guides is None and r._history_cam is None and not r._history_kept  # the viewer's history
+    assert r._history is None and not r._history_kept  # the viewer's history
     # the mirror: a full compile of the edited world has the same geometry arrays (its tree differs)
     full = sd.compile_world(_world((-0.6, 0.3, -0.4), 0.35), tables)
     assert r.arrays is r.dscene.arrays and r.arrays.sphere_data.tobytes() == full.sphere_data.tobytes()
