@@ -15,9 +15,9 @@ import os
 import numpy as np
 import torch
 
-from . import _lib, guide, motion, post, temporal, update, wf_tiles
-from .scene_data import (BUILD_COLUMNS, DeviceLayout, PRIM_QUAD, PRIM_SPHERE, PRIM_TRIANGLE, SceneArrays, camera_upload,
-                         fill_node_boxes, pack_device, shell_hint, unpack_quads, unpack_tris)
+from . import _lib, bvh as bvh_mod, guide, motion, post, temporal, tree, update, wf_tiles
+from .scene_data import (BUILD_COLUMNS, BVH_KEYS, DeviceLayout, PRIM_QUAD, PRIM_SPHERE, PRIM_TRIANGLE, SceneArrays,
+                         camera_upload, fill_node_boxes, pack_device, shell_hint, unpack_quads, unpack_tris)
 
 
 def _stream_ptr(stream=None, device=None):
@@ -50,6 +50,8 @@ class DeviceScene:
         # the reference-layout arrays the scene was packed from: update_primitives keeps them equal to the device
         self.arrays = scene if isinstance(scene, SceneArrays) else None
         self._upd = None  # update_primitives' topology, index maps and root box, made by its first call
+        self._tree = None  # tree_growth's baseline areas and result slot, made by its first call
+        self._pack = (node_bytes, leaf_order)  # rebuild packs as the scene was packed
         dev = torch.device(device if device is not None else 'cuda')
         if dev.type != 'cuda':
             raise _lib.PtmiError(f'DeviceScene needs a cuda device, got {dev}')
@@ -133,6 +135,14 @@ class DeviceScene:
                                                tris={k: v.copy() for k, v in sa.tris.items()})
         for name in ('nodes', 'spheres', 'quads', 'tris', 'ref_nodes', 'root_min', 'root_max'):
             setattr(lay, name, np.array(getattr(lay, name)))  # the layout is refreshed in place: its own copy
+        self._tree_state()  # the growth baseline is the tree as built: taken before the first update moves a box
+        self._upd = self._topology_state()
+        return self._upd
+
+    def _topology_state(self):
+        """update_primitives' topology arrays, index maps and root box for the tree ``arrays`` and ``layout`` hold."""
+        sa, lay = self.arrays, self.layout
+        b = sa.bvh
         order, level_end, slot = update.topology(b)
         ptype, pidx = b['bvh_prim_type'], b['bvh_prim_idx']
         leaves = np.nonzero(pidx >= 0)[0]
@@ -147,14 +157,13 @@ class DeviceScene:
             dev_of.append(inv)
         inner = np.nonzero(pidx < 0)[0]
         dev = self.device
-        self._upd = {
+        return {
             'order': torch.from_numpy(order).to(dev) if order.size else None,
             'slot': torch.from_numpy(slot).to(dev) if slot.size else None,
             'level_end': (C.c_int32 * max(1, level_end.size))(*level_end.tolist()), 'n_levels': int(level_end.size),
             'leaf_of': leaf_of, 'dev_of': dev_of, 'root': torch.zeros(6, dtype=torch.float32, device=dev),
             'inner': inner, 'rows': slot[inner].astype(np.int64),
             'left': b['bvh_left_child'][inner], 'right': b['bvh_right_child'][inner], 'slot_np': slot}
-        return self._upd
 
     def update_call(self, lists, stream=None, flags=None):
         """ptmi_update_primitives on this scene: ``lists`` maps a primitive type
@@ -275,6 +284,131 @@ class DeviceScene:
                 self.view.root_max[k] = float(lay.root_max[k])
             self.view.shell = int(lay.shell)
         _lib.check(_lib.load().ptmi_scene_check(self.view), 'ptmi_scene_check')
+
+    # ------------------------------------------------ tree quality, rebuild in place (ptmi.tree)
+    def _tree_state(self):
+        """tree_growth's baseline areas (taken here, on the first use, and again by
+        every rebuild) and its 16-byte result slot."""
+        if self._tree is None:
+            if self.t_ref_nodes is None:
+                raise _lib.PtmiError('tree_growth needs the scene\'s ref_nodes')
+            self._tree = {'base': torch.empty(max(4, self.view.num_bvh_nodes), dtype=torch.float32, device=self.device),
+                          'out': torch.empty(4, dtype=torch.float32, device=self.device)}
+            s = torch.cuda.current_stream(self.device)
+            self._take_baseline(s)
+            s.synchronize()  # an update on any stream may follow
+        return self._tree
+
+    def _take_baseline(self, stream):
+        with torch.cuda.device(self.device):
+            _lib.check(tree.load().ptmi_tree_areas(self.view, self._tree['base'].data_ptr(),
+                                                   _stream_ptr(stream, self.device)), 'ptmi_tree_areas')
+
+    def tree_growth(self, stream=None):
+        """``(mean, max)`` over the BVH's internal nodes of box area now / box
+        area when the tree was built or last rebuilt (ptmi_tree_growth,
+        include/ptmi_tree.h): exactly (1.0, 1.0) on an unmoved
+        or freshly rebuilt tree, growing as update_primitives scatters the
+        primitives of a refit tree. One launch on ``stream`` and one 16-byte
+        readback."""
+        st = self._tree_state()
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        with torch.cuda.device(self.device), torch.cuda.stream(s):
+            _lib.check(tree.load().ptmi_tree_growth(self.view, st['base'].data_ptr(), st['out'].data_ptr(),
+                                                    _stream_ptr(s, self.device)), 'ptmi_tree_growth')
+            out = st['out'].cpu().numpy()
+        return float(out[0]), float(out[1])
+
+    def rebuild(self, stream=None):
+        """Rebuild the BVH of the resident scene in place: the
+        native SAH builder on the mirror's builder-form arrays, pack_device of
+        the mirror with the new BVH, and its nodes, ref_nodes, spheres, quads,
+        tris and mats copied into the tensors the scene already has. No size
+        and no ``data_ptr()`` changes, so the view's pointers, an Integrator
+        and every renderer built on this scene stay valid. The view's root
+        ref, leaf depth, root box and shell hint are refreshed, ``layout`` and
+        ``arrays.bvh`` are replaced, update_primitives' topology and index
+        maps are made anew, and the growth baseline is
+        retaken: tree_growth() is (1.0, 1.0) afterwards. The builder is
+        deterministic, so ``layout`` equals pack_device of a compile of the
+        edited world byte for byte. No render of this scene may be in flight
+        (as for update_primitives); the call returns with the copies done.
+
+        Returns ``(spheres, triangles, quads)``, by type code: int32 device
+        tensors mapping each old device row to its new device row. Reference
+        primitive indices (update_primitives' arguments) do not change; device
+        rows, and so the ids of trace_guides_ids, do."""
+        self._update_state()  # the mirror (and the check that the scene was made from SceneArrays)
+        sa, old = self.arrays, self.layout
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        q, t = sa.quads, sa.tris
+        built = bvh_mod.build_sah(sa.sphere_data, np.concatenate([q['quad_Q'], q['quad_u'], q['quad_v']], axis=1),
+                                  np.concatenate([t['triangle_v0'], t['triangle_v1'], t['triangle_v2']], axis=1))
+        new_sa = dataclasses.replace(sa, bvh={k: built[k] for k in BVH_KEYS})
+        lay = pack_device(new_sa, *self._pack)
+        pairs = [(self.t_nodes, lay.nodes, old.nodes), (self.t_ref_nodes, lay.ref_nodes, old.ref_nodes),
+                 (self.t_spheres, lay.spheres, old.spheres), (self.t_quads, lay.quads, old.quads),
+                 (self.t_tris, lay.tris, old.tris), (self.t_mats, lay.mats, old.mats)]
+        for _, a, b in pairs:
+            if a.shape != b.shape:
+                raise _lib.PtmiError(f'rebuild: a packed array changed its shape ({b.shape} to {a.shape})')
+        with torch.cuda.device(self.device), torch.cuda.stream(s):
+            for dst, a, _ in pairs:
+                if a.size:
+                    dst[:a.size].copy_(torch.from_numpy(np.ascontiguousarray(a).reshape(-1)))
+            maps = tuple(torch.from_numpy(m).to(self.device) for m in tree.device_maps(old.prim_perm, lay.prim_perm))
+        v = self.view
+        v.root_ref, v.max_leaf_depth, v.shell = lay.root_ref, lay.max_leaf_depth, int(lay.shell)
+        for k in range(3):
+            v.root_min[k] = float(lay.root_min[k])
+            v.root_max[k] = float(lay.root_max[k])
+        self.layout, self.arrays = lay, new_sa
+        self._upd = self._topology_state()  # leaf_of and dev_of of the new tree; the mirror is this scene's own already
+        self._take_baseline(s)
+        s.synchronize()
+        _lib.check(_lib.load().ptmi_scene_check(v), 'ptmi_scene_check')
+        return maps
+
+    def remap_ids(self, ids, maps, out=None, stream=None):
+        """An id image (trace_guides_ids) of this scene before a rebuild carried
+        to the device rows after it (ptmi_ids_remap, include/ptmi_tree.h):
+        ``maps`` is rebuild()'s return value; an id whose type, row or map entry
+        is out of range becomes -1. Returns a new tensor, or ``out`` (which may
+        be ``ids`` itself). Asynchronous on ``stream``."""
+        _check_tensor('ids', ids, ('H', 'W'), torch.int32, self.device)
+        counts = (self.layout.num_spheres, self.layout.num_triangles, self.layout.num_quads)
+        maps = tuple(maps)
+        if len(maps) != 3:
+            raise _lib.PtmiError('maps must be (spheres, triangles, quads)')
+        for m, n, name in zip(maps, counts, ('spheres', 'triangles', 'quads')):
+            _check_tensor(f'maps: {name}', m, (n,), torch.int32, self.device)
+        with torch.cuda.device(self.device):
+            if out is None:
+                with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.device)):
+                    out = torch.empty_like(ids)
+            _check_tensor('out', out, tuple(ids.shape), torch.int32, self.device)
+            ptr = [m.data_ptr() if n else None for m, n in zip(maps, counts)]
+            _lib.check(tree.load().ptmi_ids_remap(ids.data_ptr(), out.data_ptr(), ids.numel(), ptr[0], ptr[1], ptr[2],
+                                                  tree.IdsCounts(*counts), _stream_ptr(stream, self.device)),
+                       'ptmi_ids_remap')
+        return out
+
+    def permute_rows(self, rows, maps, stream=None):
+        """``primitive_rows()`` taken before a rebuild, in the device order after
+        it: row ``maps[t][k]`` of the result is row k of ``rows``. ``rows`` is
+        (spheres, quads, tris) as primitive_rows returns them, ``maps`` is
+        rebuild()'s (spheres, triangles, quads)."""
+        lay = self.layout
+        out = []
+        with torch.cuda.device(self.device), torch.cuda.stream(
+                stream if stream is not None else torch.cuda.current_stream(self.device)):
+            for r, m, n, w in ((rows[0], maps[0], lay.num_spheres, 4), (rows[1], maps[2], lay.num_quads, 16),
+                               (rows[2], maps[1], lay.num_triangles, 12)):
+                new = r.clone()
+                if n:
+                    new[:n * w].view(n, w)[m.long()] = r[:n * w].view(n, w)
+                out.append(new)
+        return tuple(out)
 
 
 def make_frame(cam, bg, max_depth, seed, width, height, window=None, band=(1, 1, 0), traversal='stack'):

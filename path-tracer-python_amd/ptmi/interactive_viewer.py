@@ -148,22 +148,40 @@ class InteractiveViewer(MI355XRenderer):
         self.is_rendering_active = True
         print(f"\n{'─' * 60}\nCamera rotated - restarting render from sample 0\n{'─' * 60}")
 
-    def update_primitives(self, spheres=None, quads=None, triangles=None):
-        """MI355XRenderer.update_primitives. Without ``motion`` the temporal
-        history is dropped with the image. A ``motion=True``
-        viewer that has a rendered history keeps it: the update runs, and the
-        history is reprojected from the camera, guides, ids and primitive rows
-        it was rendered with to the current camera and scene,
-        by the rule of ``_restart_with_history``: a second update, or a camera
-        move, with no sample in between reprojects the rendered history again,
-        not the reprojected one."""
+    def update_primitives(self, spheres=None, quads=None, triangles=None, rebuild=False, rebuild_growth=None):
+        """MI355XRenderer.update_primitives, ``rebuild`` and ``rebuild_growth``
+        included. What becomes of the temporal history is
+        ``_change_scene``'s rule."""
+        threshold = self._rebuild_threshold(rebuild, rebuild_growth)
+
+        def change():
+            self._apply_update(spheres, quads, triangles)
+            return self._rebuild_scene() if self._wants_rebuild(rebuild, threshold) else None
+        return self._change_scene(change, 'Scene updated')
+
+    def rebuild_bvh(self):
+        """MI355XRenderer.rebuild_bvh, the temporal history treated as by ``update_primitives``."""
+        return self._change_scene(self._rebuild_scene, 'BVH rebuilt')
+
+    def _change_scene(self, change, what):
+        """Run ``change()``, which alters the scene and returns a rebuild's row
+        maps or None. Without ``motion`` the temporal history is dropped with
+        the image. A ``motion=True`` viewer that has a rendered
+        history keeps it: the history is reprojected from the camera, guides,
+        ids and primitive rows it was rendered with to the current camera and
+        scene, its ids and rows carried to the new device order
+        first if the BVH was rebuilt, by the rule of ``_restart_with_history``:
+        a second change, or a camera move, with no sample in between
+        reprojects the rendered history again, not the reprojected one."""
         if self.motion and self.stats is not None and self._history is not None and \
                 self._history.ids is not None and (self.current_sample > 0 or self._history_kept):
             if self._history.rows is None:  # the scene still is what the history was rendered with
                 self._history.rows = self.dscene.primitive_rows()
-            self._apply_update(spheres, quads, triangles)
-            return self._restart_with_history('Scene updated')
-        super().update_primitives(spheres, quads, triangles)
+            maps = change()
+            if maps is not None:
+                self._history = self._history_across_rebuild(self._history, maps)
+            return self._restart_with_history(what)
+        self._after_scene_change(None, change(), {})
         self._history, self._history_kept = None, False
         self.history_fraction = None
         self.render_start_time = time.time()

@@ -47,7 +47,10 @@ camera move. Derived state: not checkpointed.
 Scene updates (no counterpart in the reference): ``update_primitives`` moves
 spheres, quads and triangles of the resident scene and refits the BVH on the
 device instead of building a new renderer; ``primitives`` lists
-the objects by the indices it takes. The image starts over.
+the objects by the indices it takes. The image starts over. ``tree_growth()``
+says how far the refit tree's boxes have grown since it was built, and
+``rebuild_bvh()`` / ``update_primitives(rebuild=True | 'auto')`` rebuild the
+BVH of the resident scene in place, history included.
 """
 from __future__ import annotations
 
@@ -58,7 +61,7 @@ import time
 import numpy as np
 import torch
 
-from . import _lib, bvh as bvh_mod, core, device, scene_compiler
+from . import _lib, bvh as bvh_mod, core, device, scene_compiler, tree as tree_mod
 from .scene_data import SceneArrays
 
 # kernels.py:746: the reference's switch between its front-to-back stack
@@ -120,6 +123,9 @@ class MI355XRenderer:
         self._history_spare = None
         # update_primitives(): bumped on every scene update; part of the guides' cache key
         self.scene_revision = 0
+        # rebuild_bvh() and update_primitives(rebuild=...): rebuilds done, and the (mean, max) growth 'auto' last read
+        self.bvh_rebuilds = 0
+        self.last_tree_growth = None
         # launches per progress report: one launch renders many samples (path regeneration)
         self.samples_per_launch = int(samples_per_launch)
         device.require_gpu()
@@ -404,7 +410,8 @@ class MI355XRenderer:
 
     _REBUILD = 'for any other edit build a new MI355XRenderer from the edited world'
 
-    def update_primitives(self, spheres=None, quads=None, triangles=None, keep_history=False, **params):
+    def update_primitives(self, spheres=None, quads=None, triangles=None, keep_history=False, rebuild=False,
+                          rebuild_growth=None, **params):
         """Move primitives of the resident scene and refit its BVH on the device
         (DeviceScene.update_primitives, include/ptmi_update.h).
         Each argument maps a reference primitive index (the primitive's place
@@ -413,7 +420,7 @@ class MI355XRenderer:
         the object must be of the list's kind and compile to the material
         record the primitive has; counts, order, media and the BVH topology
         stay (a refit tree traverses slower the further objects scatter).
-        Anything else is a ValueError: the rebuild path is a new renderer.
+        Anything else is a ValueError: that path is a new renderer.
 
         The image starts over: the accumulator is cleared, the adaptive state
         is reset as for a new adaptive render, ``denoised`` and the
@@ -429,20 +436,113 @@ class MI355XRenderer:
         and ``stats`` to where every surface point went, with ``params`` as
         its parameters. The accumulator is not cleared and ``current_sample``
         stays; the tile states start over and ``denoised`` is dropped. Returns
-        the fraction of pixels with history (None without keep_history)."""
+        the fraction of pixels with history (None without keep_history).
+
+        ``rebuild``: False, the default, refits only and
+        launches nothing else. True rebuilds the BVH in place after the refit
+        (``rebuild_bvh``). 'auto' reads the refit tree's mean box growth
+        (``tree_growth``, kept as ``last_tree_growth``) and rebuilds if it
+        exceeds ``rebuild_growth`` (default ``ptmi.tree.REBUILD_GROWTH``; a
+        ValueError where neither is set). The default is the growth at which
+        a rebuild pays for itself within one 64-spp 800x800 step, where the
+        refit tree already renders at about half the rebuilt rate: a
+        loop that renders several steps per update should pass a lower one
+        (DESIGN.md §20 has the sweep). A rebuild bumps ``scene_revision``
+        once more and does to the image what the update does: with
+        ``keep_history`` the history's ids and primitive rows are carried to
+        the new device order before the reprojection. Reference indices do
+        not change across a rebuild; the device rows in ``guides_ids()`` do."""
+        threshold = self._rebuild_threshold(rebuild, rebuild_growth)
+        history = self._take_history(keep_history, params)
+        self._apply_update(spheres, quads, triangles)
+        maps = self._rebuild_scene() if self._wants_rebuild(rebuild, threshold) else None
+        return self._after_scene_change(history, maps, params)
+
+    def _take_history(self, keep_history, params):
+        """The _History of the image before a scene change that keeps it, else None (and then no ``params``)."""
         if keep_history:
             if self.stats is None:
                 raise ValueError('keep_history=True needs stats: render through the stats path (render_adaptive) first')
-            history = _History(self.frame.cam, *self.guides_ids(), self.dscene.primitive_rows())
-        elif params:
+            return _History(self.frame.cam, *self.guides_ids(), self.dscene.primitive_rows())
+        if params:
             raise ValueError(f'{sorted(params)} are reprojection parameters: they need keep_history=True')
-        self._apply_update(spheres, quads, triangles)
-        if keep_history:
+        return None
+
+    def _after_scene_change(self, history, maps, params):
+        """What becomes of the image after an update, a rebuild (``maps``: its
+        row maps, else None) or both: reprojected from ``history``, or started over."""
+        if history is not None:
+            if maps is not None:
+                history = self._history_across_rebuild(history, maps)
             return self._reproject_from(history, **params)
         self._restart_image()
         self.adaptive_passes = []
         self._history_spare = None
         self._guide_cache = (None, None, None)
+
+    # ------------------------------------------------- tree quality and rebuild
+    def tree_growth(self):
+        """``(mean, max)`` growth of the BVH's internal boxes since the tree was
+        built or last rebuilt (DeviceScene.tree_growth):
+        (1.0, 1.0) until an update moves something."""
+        return self.dscene.tree_growth()
+
+    @staticmethod
+    def _rebuild_threshold(rebuild, rebuild_growth):
+        """update_primitives' ``rebuild`` and ``rebuild_growth`` checked: the growth
+        'auto' rebuilds above, else None."""
+        if not (rebuild is True or rebuild is False or rebuild == 'auto'):
+            raise ValueError(f"rebuild must be False, True or 'auto', not {rebuild!r}")
+        if rebuild != 'auto':
+            if rebuild_growth is not None:
+                raise ValueError("rebuild_growth is the threshold of rebuild='auto'")
+            return None
+        if rebuild_growth is None:
+            rebuild_growth = tree_mod.REBUILD_GROWTH
+        if rebuild_growth is None:
+            raise ValueError("rebuild='auto' needs rebuild_growth=: no default has been measured "
+                             "(ptmi.tree.REBUILD_GROWTH)")
+        rebuild_growth = float(rebuild_growth)
+        if not rebuild_growth >= 1.0:
+            raise ValueError('rebuild_growth is a mean box-area growth: at least 1.0')
+        return rebuild_growth
+
+    def _wants_rebuild(self, rebuild, threshold):
+        """After the refit: rebuild now? 'auto' reads the tree's mean growth (one launch, one 16-byte readback)."""
+        if rebuild == 'auto':
+            self.last_tree_growth = self.dscene.tree_growth()
+            return self.last_tree_growth[0] > threshold
+        return bool(rebuild)
+
+    def _rebuild_scene(self):
+        """DeviceScene.rebuild with no render in flight; bumps ``scene_revision``. Returns its row maps."""
+        torch.cuda.synchronize(self.dscene.device)
+        maps = self.dscene.rebuild()
+        self.arrays = self.dscene.arrays
+        self.scene_revision += 1
+        self.bvh_rebuilds += 1
+        return maps
+
+    def _history_across_rebuild(self, history, maps):
+        """A history taken before a rebuild in the device order after it: its ids
+        remapped (ptmi_ids_remap) and its primitive rows permuted."""
+        return _History(history.camera, history.guides, self.dscene.remap_ids(history.ids, maps),
+                        self.dscene.permute_rows(history.rows, maps))
+
+    def rebuild_bvh(self, keep_history=False, **params):
+        """Rebuild the resident scene's BVH in place (DeviceScene.rebuild,
+        DESIGN.md §20): what a new renderer of the edited world would build,
+        without a new renderer. The device tensors, their pointers, this
+        renderer and its integrator stay; ``scene_revision`` is bumped and
+        ``bvh_rebuilds`` counted. The image is treated as by
+        ``update_primitives``: started over, or with ``keep_history=True``
+        reprojected (``params`` as there; the history's ids and rows are
+        carried to the new device order first). The reference indices that
+        ``update_primitives`` and ``primitives`` take do not change; the
+        device rows in ``guides_ids()``'s id image do. Returns the fraction of
+        pixels with history (None without keep_history)."""
+        history = self._take_history(keep_history, params)
+        return self._after_scene_change(history, self._rebuild_scene(), params)
 
     def _apply_update(self, spheres, quads, triangles):
         """update_primitives' checks and the update itself, up to the bumped
