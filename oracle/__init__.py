@@ -5,7 +5,8 @@ reference's own array layout. Only tests/, __graft_entry__.smoke() and
 bench.py's cpu_baseline leg may import this module, and only as the checker.
 Scene/BVH arrays are pinned to the reference by tests/golden fixtures; pixel
 values are pinned to this restatement (Taichi cannot run: parity vs Taichi
-pixels is unpinned).
+pixels is unpinned), and the restatement, path by path, to the
+reference's kernel text run over a Taichi stand-in (tests/test_kernel_paths.py).
 """
 from __future__ import annotations
 
@@ -48,6 +49,16 @@ class OrStats(C.Structure):
                 ('depth_cap', C.c_uint64)]
 
 
+class OrSeg(C.Structure):
+    _fields_ = [('rng_n', C.c_uint32), ('hit', C.c_int32), ('t', C.c_float), ('prim_type', C.c_int32),
+                ('prim_idx', C.c_int32), ('kind', C.c_int32)]
+
+
+# or_seg.kind (pt_oracle.h OR_SEG_*)
+SEG_KINDS = ('surface', 'medium_scatter', 'passthrough', 'fallback', 'miss')
+SEG_DTYPE = np.dtype([('rng_n', np.uint32), ('hit', np.int32), ('t', np.float32), ('prim_type', np.int32),
+                      ('prim_idx', np.int32), ('kind', np.int32)])
+
 _lib = None
 
 
@@ -73,6 +84,9 @@ def load_variant(path):
     lib.or_traverse.argtypes = [C.POINTER(OrScene), C.c_int, P, P, C.c_float, C.c_float, P, P, P]
     lib.or_trace_path.argtypes = [C.POINTER(OrScene), C.POINTER(OrFrame), C.c_int, C.c_int, C.c_int, C.c_int,
                                   P, C.POINTER(OrStats)]
+    lib.or_trace_path_log.argtypes = [C.POINTER(OrScene), C.POINTER(OrFrame), C.c_int, C.c_int, C.c_int,
+                                      C.c_int, P, C.POINTER(OrStats), P, C.c_int, P]
+    lib.or_trace_path_log.restype = C.c_int
     lib.or_math_probe.argtypes = [C.c_int, P, P, P, C.c_int]
     lib.or_rng_probe.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, P, P]
     lib.or_func_probe.argtypes = [C.POINTER(OrScene), C.c_int, P, P, C.c_int]
@@ -179,6 +193,22 @@ def traverse(oscene, o, d, tmin=0.001, tmax=1e10, traversal='stack'):
     ix = np.zeros(1, np.int32)
     hit = load().or_traverse(C.byref(oscene.s), TRAVERSALS[traversal], _ptr(o), _ptr(d), tmin, tmax, _ptr(t), _ptr(ty), _ptr(ix))
     return bool(hit), float(t[0]), int(ty[0]), int(ix[0])
+
+
+def trace_path_log(oscene, frame, variant, px, py, sample, max_segs=256):
+    """One path through or_trace_path's code with its segment records.
+    Returns (colour (3,) f32, counters dict, records (SEG_DTYPE array, one per
+    segment), number of ti.random() draws the path consumed)."""
+    color = np.zeros(3, np.float32)
+    segs = np.zeros(max_segs, SEG_DTYPE)
+    draws = np.zeros(1, np.uint32)
+    st = OrStats()
+    n = load().or_trace_path_log(C.byref(oscene.s), C.byref(frame), 0 if variant == 'mk' else 1, px, py, sample,
+                                 _ptr(color), C.byref(st), _ptr(segs), max_segs, _ptr(draws))
+    if n > max_segs:
+        raise RuntimeError(f'path has {n} segments, more than max_segs = {max_segs}')
+    return color, {'segments': st.segments, 'medium': st.medium, 'paths': st.paths, 'rr': st.rr,
+                   'depth_cap': st.depth_cap}, segs[:n], int(draws[0])
 
 
 MATH_FNS = {'sin': 0, 'cos': 1, 'log': 2, 'acos': 3, 'atan2': 4, 'pow5': 5, 'div_by': 6}

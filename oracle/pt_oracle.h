@@ -9,7 +9,9 @@
  *
  * Pixel parity against Taichi itself is unpinned (Taichi cannot run here,
  * SURVEY.md §8c); the scene/BVH arrays this oracle consumes are pinned
- * bit-exactly by tests/golden fixtures generated from the reference.
+ * bit-exactly by tests/golden fixtures generated from the reference, and its
+ * paths by the reference's kernel text run over a Taichi stand-in
+ * (tests/golden/kernel_paths_*.npz, tests/test_kernel_paths.py).
  */
 #ifndef PT_ORACLE_H
 #define PT_ORACLE_H
@@ -72,6 +74,22 @@ typedef struct or_stats {
     uint64_t depth_cap;  /* paths ended by the depth / wave budget (kernels.py:1139-1141, 1383; renderer.py:313) */
 } or_stats;
 
+/* One record per segment of a path (or_trace_path_log): a traverse_bvh call
+ * from the depth loop (kernels.py:1056) or a wave (:1253). */
+enum { OR_SEG_SURFACE = 0,         /* hit, shaded as a surface (kernels.py:1120-1129, 1358-1363) */
+       OR_SEG_MEDIUM_SCATTER = 1,  /* medium boundary, scattered inside (:1082-1097, 1331-1340) */
+       OR_SEG_PASSTHROUGH = 2,     /* medium boundary, left without scattering (:1100-1110, 1342-1350) */
+       OR_SEG_FALLBACK = 3,        /* medium boundary without an exit, shaded as a surface (:1111-1119, 1352-1357) */
+       OR_SEG_MISS = 4 };
+
+typedef struct or_seg {
+    uint32_t rng_n;       /* the path's draw counter when the segment's traversal starts */
+    int32_t hit;
+    float t;              /* 0 on a miss */
+    int32_t prim_type, prim_idx;   /* -1 on a miss */
+    int32_t kind;         /* OR_SEG_* */
+} or_seg;
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -88,6 +106,12 @@ int or_traverse(const or_scene *sc, int traversal, const float *o, const float *
 /* one path: returns its colour contribution and counters */
 int or_trace_path(const or_scene *sc, const or_frame *fr, int variant, int px, int py, int sample,
                   float *color_out, or_stats *stats);
+/* or_trace_path (the same code path) that also writes the path's first max_segs
+ * segment records to the caller's segs and the number of ti.random() draws the
+ * path consumed to draws_out (either may be NULL). Returns the path's number of
+ * segments, which may exceed max_segs. */
+int or_trace_path_log(const or_scene *sc, const or_frame *fr, int variant, int px, int py, int sample,
+                      float *color_out, or_stats *stats, or_seg *segs, int max_segs, uint32_t *draws_out);
 /* math / rng probes for the known-answer tests */
 void or_math_probe(int fn, const float *x, const float *y, float *out, int n);
 /* per-function probes (known-answer tests against the reference's own Python,
