@@ -16,16 +16,18 @@ import numpy as np
 import torch
 
 from . import _lib, bvh as bvh_mod, guide, motion, post, temporal, tree, update, wf_tiles
-from .scene_data import (BUILD_COLUMNS, BVH_KEYS, DeviceLayout, PRIM_QUAD, PRIM_SPHERE, PRIM_TRIANGLE, SceneArrays,
-                         camera_upload, fill_node_boxes, pack_device, shell_hint, unpack_quads, unpack_tris)
+from .scene_data import (BVH_KEYS, ByCode, ByStorage, DeviceLayout, STORAGE, SceneArrays, camera_upload,
+                         counts_by_code, pack_device)
+
+
+def _stream_or_current(stream, device=None):
+    return stream if stream is not None else torch.cuda.current_stream(device)
 
 
 def _stream_ptr(stream=None, device=None):
-    if stream is None:
-        stream = torch.cuda.current_stream(device)
-    elif device is not None and stream.device != device:
+    if stream is not None and device is not None and stream.device != device:
         raise _lib.PtmiError(f'stream is on {stream.device}, the scene on {device}')
-    return C.c_void_p(stream.cuda_stream)
+    return C.c_void_p(_stream_or_current(stream, device).cuda_stream)
 
 
 def require_gpu():
@@ -66,28 +68,20 @@ class DeviceScene:
                 a = np.zeros(4, dtype=a.dtype)  # keep a valid 16-B aligned pointer
             return torch.from_numpy(a.reshape(-1).copy()).to(self.device)
 
+        v = _lib.SceneView()
         self.t_nodes = up(layout.nodes)
-        self.t_spheres = up(layout.spheres)
-        self.t_quads = up(layout.quads)
-        self.t_tris = up(layout.tris)
+        for k in STORAGE:  # t_spheres, t_quads, t_tris
+            setattr(self, k.tensor, up(getattr(layout, k.rows)))
+            setattr(v, k.rows, getattr(self, k.tensor).data_ptr())
+            setattr(v, k.count, getattr(layout, k.count))
         self.t_mats = up(layout.mats)
         self.t_texels = up(layout.texels.view(np.int32))
         self.t_pvec = up(layout.perlin_vec)
         self.t_perm = up(layout.perlin_perm)
         self.t_ref_nodes = up(layout.ref_nodes) if layout.ref_nodes is not None else None
-        v = _lib.SceneView()
         v.nodes = self.t_nodes.data_ptr()
         v.n_inner = layout.n_inner
-        v.root_ref = layout.root_ref
-        for k in range(3):
-            v.root_min[k] = float(layout.root_min[k])
-            v.root_max[k] = float(layout.root_max[k])
-        v.max_leaf_depth = layout.max_leaf_depth
-        v.spheres = self.t_spheres.data_ptr()
-        v.quads = self.t_quads.data_ptr()
-        v.tris = self.t_tris.data_ptr()
         v.mats = self.t_mats.data_ptr()
-        v.num_spheres, v.num_quads, v.num_triangles = layout.num_spheres, layout.num_quads, layout.num_triangles
         v.texels = self.t_texels.data_ptr()
         v.num_images = len(layout.img_w)
         for k in range(len(layout.img_w)):
@@ -99,9 +93,15 @@ class DeviceScene:
         if self.t_ref_nodes is not None:
             v.ref_nodes = self.t_ref_nodes.data_ptr()
         v.num_bvh_nodes = layout.num_bvh_nodes if layout.ref_nodes is not None else \
-            (2 * (layout.n_inner + 1) - 1 if layout.num_spheres + layout.num_quads + layout.num_triangles else 0)
-        v.shell = int(layout.shell)
+            (2 * (layout.n_inner + 1) - 1 if sum(counts_by_code(layout)) else 0)
         self.view = v
+        self._set_tree(layout)
+
+    def _set_tree(self, lay):
+        """The view's tree fields (root ref, leaf depth, root box, shell hint) from a layout, and the view checked."""
+        v = self.view
+        v.root_ref, v.max_leaf_depth, v.shell = lay.root_ref, lay.max_leaf_depth, int(lay.shell)
+        v.root_min[:], v.root_max[:] = [float(x) for x in lay.root_min], [float(x) for x in lay.root_max]
         _lib.check(_lib.load().ptmi_scene_check(v), 'ptmi_scene_check')
 
     @classmethod
@@ -110,12 +110,11 @@ class DeviceScene:
 
     def primitive_rows(self, stream=None):
         """Device-to-device copies of the sphere, quad and triangle row tensors,
-        ``(spheres, quads, tris)``: the "previous rows" of a motion-aware
-        reprojection (Integrator.reproject_moved), taken before an update.
-        Asynchronous on ``stream``."""
-        with torch.cuda.device(self.device), torch.cuda.stream(
-                stream if stream is not None else torch.cuda.current_stream(self.device)):
-            return self.t_spheres.clone(), self.t_quads.clone(), self.t_tris.clone()
+        a ByStorage ``(spheres, quads, tris)``: the "previous rows" of a
+        motion-aware reprojection (Integrator.reproject_moved), taken before an
+        update. Asynchronous on ``stream``."""
+        with torch.cuda.device(self.device), torch.cuda.stream(_stream_or_current(stream, self.device)):
+            return ByStorage(*(getattr(self, k.tensor).clone() for k in STORAGE))
 
     # ------------------------------------------------ scene updates (ptmi.update)
     def _update_state(self):
@@ -141,29 +140,12 @@ class DeviceScene:
 
     def _topology_state(self):
         """update_primitives' topology arrays, index maps and root box for the tree ``arrays`` and ``layout`` hold."""
-        sa, lay = self.arrays, self.layout
-        b = sa.bvh
-        order, level_end, slot = update.topology(b)
-        ptype, pidx = b['bvh_prim_type'], b['bvh_prim_idx']
-        leaves = np.nonzero(pidx >= 0)[0]
-        leaf_of, dev_of = [], []
-        for t, n in enumerate((sa.num_spheres, sa.num_triangles, sa.num_quads)):  # by type code
-            sel = leaves[ptype[leaves] == t]
-            lo = np.full(n, -1, np.int64)
-            lo[pidx[sel]] = sel
-            inv = np.empty(n, np.int64)
-            inv[lay.prim_perm[t]] = np.arange(n)
-            leaf_of.append(lo)
-            dev_of.append(inv)
-        inner = np.nonzero(pidx < 0)[0]
-        dev = self.device
-        return {
-            'order': torch.from_numpy(order).to(dev) if order.size else None,
-            'slot': torch.from_numpy(slot).to(dev) if slot.size else None,
-            'level_end': (C.c_int32 * max(1, level_end.size))(*level_end.tolist()), 'n_levels': int(level_end.size),
-            'leaf_of': leaf_of, 'dev_of': dev_of, 'root': torch.zeros(6, dtype=torch.float32, device=dev),
-            'inner': inner, 'rows': slot[inner].astype(np.int64),
-            'left': b['bvh_left_child'][inner], 'right': b['bvh_right_child'][inner], 'slot_np': slot}
+        maps = update.index_maps(self.arrays.bvh, self.layout.prim_perm, counts_by_code(self.arrays))
+        order, level_end, slot, dev = maps['order'], maps['level_end'], maps['slot_np'], self.device
+        return dict(maps, order=torch.from_numpy(order).to(dev) if order.size else None,
+                    slot=torch.from_numpy(slot).to(dev) if slot.size else None,
+                    level_end=(C.c_int32 * max(1, level_end.size))(*level_end.tolist()), n_levels=int(level_end.size),
+                    root=torch.zeros(6, dtype=torch.float32, device=dev))
 
     def update_call(self, lists, stream=None, flags=None):
         """ptmi_update_primitives on this scene: ``lists`` maps a primitive type
@@ -175,10 +157,8 @@ class DeviceScene:
         st = self._update_state()
         if flags is None:
             flags = update.refit_flags(self.layout.n_inner, st['n_levels'])
-        arg = []
-        for t in (PRIM_SPHERE, PRIM_QUAD, PRIM_TRIANGLE):
-            e = lists.get(t)
-            arg.append(C.byref(update.UpdateList(*e)) if e is not None and e[4] else None)
+        arg = [C.byref(update.UpdateList(*e)) if e is not None and e[4] else None
+               for e in (lists.get(k.code) for k in STORAGE)]
         topo = update.UpdateTopology(st['order'].data_ptr() if st['order'] is not None else None,
                                      st['slot'].data_ptr() if st['slot'] is not None else None,
                                      st['level_end'], st['n_levels'], int(flags))
@@ -201,46 +181,16 @@ class DeviceScene:
         (scene_data.find_shell on the mirror; 0 if the claim no longer holds).
         Topology, materials and counts do not change: for anything else build a
         new DeviceScene. ``flags`` as for update_call (same bits either way)."""
-        edits = self._check_edits(spheres, quads, triangles)
-        self._upload_edits(edits, stream, flags)
-        (stream if stream is not None else torch.cuda.current_stream(self.device)).synchronize()
-        self._refresh_mirror(edits)
-
-    def _check_edits(self, spheres, quads, triangles):
-        """update_primitives' arguments checked: {type code: (int64 indices, (n, row floats) rows, (n, build floats)
-        build records)} of the non-empty ones. Nothing is uploaded."""
-        st, edits = self._update_state(), {}
-        for t, arg, name in ((PRIM_SPHERE, spheres, 'spheres'), (PRIM_QUAD, quads, 'quads'),
-                             (PRIM_TRIANGLE, triangles, 'triangles')):
-            if arg is None:
-                continue
-            idx, rows, build = arg
-            idx = np.asarray(idx)
-            n, count = int(idx.size), int(st['leaf_of'][t].shape[0])
-            if idx.ndim != 1 or (n and not np.issubdtype(idx.dtype, np.integer)):
-                raise ValueError(f'{name}: indices must be a 1-D integer array')
-            idx = idx.astype(np.int64)
-            if n and (idx.min() < 0 or idx.max() >= count):
-                raise ValueError(f'{name}: an index is outside [0, {count})')
-            if np.unique(idx).size != n:
-                raise ValueError(f'{name}: an index is repeated')
-            rows, build = np.ascontiguousarray(rows, np.float32), np.ascontiguousarray(build, np.float32)
-            if rows.size != n * update.ROW_FLOATS[t] or build.size != n * update.BUILD_FLOATS[t]:
-                raise ValueError(f'{name}: rows must be (n, {update.ROW_FLOATS[t]}) and build records '
-                                 f'(n, {update.BUILD_FLOATS[t]}) f32')
-            rows, build = rows.reshape(n, update.ROW_FLOATS[t]), build.reshape(n, update.BUILD_FLOATS[t])
-            if not (np.isfinite(rows).all() and np.isfinite(build).all()):
-                raise ValueError(f'{name}: rows and build records must be finite')
-            points = rows[:, BUILD_COLUMNS[t]]
-            if points.tobytes() != build[:, :points.shape[1]].tobytes():
-                raise ValueError(f'{name}: a row and its build record name different points')
-            if n:
-                edits[t] = (idx, rows, build)
-        return edits
-
-    def _upload_edits(self, edits, stream, flags):
-        """The checked edits to the device in one int and one float tensor, and update_call on them."""
         st = self._update_state()
+        edits = update.check_edits(counts_by_code(self.layout), spheres, quads, triangles)
+        self._upload_edits(st, edits, stream, flags)
+        _stream_or_current(stream, self.device).synchronize()
+        update.refresh_mirror(self.arrays, self.layout, st, edits,
+                              self.t_ref_nodes.cpu().numpy() if self.arrays.num_bvh_nodes else None)
+        self._set_tree(self.layout)
+
+    def _upload_edits(self, st, edits, stream, flags):
+        """The checked edits to the device in one int and one float tensor, and update_call on them."""
         ints, floats, lists, ni, nf = [], [], {}, 0, 0
         for t, (idx, rows, build) in edits.items():
             n = idx.size
@@ -254,36 +204,6 @@ class DeviceScene:
             pi, pf = ti.data_ptr(), tf.data_ptr()
             lists = {t: (pi + 4 * a, pi + 4 * b, pf + 4 * c, pf + 4 * d, n) for t, (a, b, c, d, n) in lists.items()}
         self.update_call(lists, stream, flags)
-
-    def _refresh_mirror(self, edits):
-        """``arrays``, ``layout`` and the view after a finished update: the boxes
-        from the device, the edited primitives from the arguments."""
-        st, sa, lay = self._update_state(), self.arrays, self.layout
-        nb = sa.num_bvh_nodes
-        if nb:
-            rn = self.t_ref_nodes.cpu().numpy().reshape(-1, 12)
-            sa.bvh['bvh_bbox_min'][:] = rn[:nb, 0:3]
-            sa.bvh['bvh_bbox_max'][:] = rn[:nb, 4:7]
-        for t, (idx, rows, build) in edits.items():
-            if t == PRIM_SPHERE:
-                sa.sphere_data[idx] = rows
-            else:
-                mirror, new = (sa.quads, unpack_quads(rows)) if t == PRIM_QUAD else (sa.tris, unpack_tris(rows, build))
-                for key, values in new.items():
-                    mirror[key][idx] = values
-            (lay.spheres, lay.tris, lay.quads)[t][st['dev_of'][t][idx]] = rows  # by type code
-        if nb:
-            lay.ref_nodes[:] = rn[:nb]
-            if st['inner'].size:
-                fill_node_boxes(lay.nodes, st['rows'], sa.bvh['bvh_bbox_min'], sa.bvh['bvh_bbox_max'], st['left'],
-                                st['right'])
-            lay.root_min[:], lay.root_max[:] = rn[0, 0:3], rn[0, 4:7]
-            lay.shell = shell_hint(sa, st['slot_np'], lay.max_leaf_depth, lay.nodes.shape[1] * 4)
-            for k in range(3):
-                self.view.root_min[k] = float(lay.root_min[k])
-                self.view.root_max[k] = float(lay.root_max[k])
-            self.view.shell = int(lay.shell)
-        _lib.check(_lib.load().ptmi_scene_check(self.view), 'ptmi_scene_check')
 
     # ------------------------------------------------ tree quality, rebuild in place (ptmi.tree)
     def _tree_state(self):
@@ -312,7 +232,7 @@ class DeviceScene:
         primitives of a refit tree. One launch on ``stream`` and one 16-byte
         readback."""
         st = self._tree_state()
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        s = _stream_or_current(stream, self.device)
         with torch.cuda.device(self.device), torch.cuda.stream(s):
             _lib.check(tree.load().ptmi_tree_growth(self.view, st['base'].data_ptr(), st['out'].data_ptr(),
                                                     _stream_ptr(s, self.device)), 'ptmi_tree_growth')
@@ -334,21 +254,21 @@ class DeviceScene:
         edited world byte for byte. No render of this scene may be in flight
         (as for update_primitives); the call returns with the copies done.
 
-        Returns ``(spheres, triangles, quads)``, by type code: int32 device
+        Returns a ByCode ``(spheres, triangles, quads)`` of int32 device
         tensors mapping each old device row to its new device row. Reference
         primitive indices (update_primitives' arguments) do not change; device
         rows, and so the ids of trace_guides_ids, do."""
         self._update_state()  # the mirror (and the check that the scene was made from SceneArrays)
         sa, old = self.arrays, self.layout
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        s = _stream_or_current(stream, self.device)
         q, t = sa.quads, sa.tris
         built = bvh_mod.build_sah(sa.sphere_data, np.concatenate([q['quad_Q'], q['quad_u'], q['quad_v']], axis=1),
                                   np.concatenate([t['triangle_v0'], t['triangle_v1'], t['triangle_v2']], axis=1))
         new_sa = dataclasses.replace(sa, bvh={k: built[k] for k in BVH_KEYS})
         lay = pack_device(new_sa, *self._pack)
-        pairs = [(self.t_nodes, lay.nodes, old.nodes), (self.t_ref_nodes, lay.ref_nodes, old.ref_nodes),
-                 (self.t_spheres, lay.spheres, old.spheres), (self.t_quads, lay.quads, old.quads),
-                 (self.t_tris, lay.tris, old.tris), (self.t_mats, lay.mats, old.mats)]
+        pairs = [(self.t_nodes, lay.nodes, old.nodes), (self.t_ref_nodes, lay.ref_nodes, old.ref_nodes)]
+        pairs += [(getattr(self, k.tensor), getattr(lay, k.rows), getattr(old, k.rows)) for k in STORAGE]
+        pairs.append((self.t_mats, lay.mats, old.mats))
         for _, a, b in pairs:
             if a.shape != b.shape:
                 raise _lib.PtmiError(f'rebuild: a packed array changed its shape ({b.shape} to {a.shape})')
@@ -356,17 +276,13 @@ class DeviceScene:
             for dst, a, _ in pairs:
                 if a.size:
                     dst[:a.size].copy_(torch.from_numpy(np.ascontiguousarray(a).reshape(-1)))
-            maps = tuple(torch.from_numpy(m).to(self.device) for m in tree.device_maps(old.prim_perm, lay.prim_perm))
-        v = self.view
-        v.root_ref, v.max_leaf_depth, v.shell = lay.root_ref, lay.max_leaf_depth, int(lay.shell)
-        for k in range(3):
-            v.root_min[k] = float(lay.root_min[k])
-            v.root_max[k] = float(lay.root_max[k])
+            maps = ByCode(*(torch.from_numpy(m).to(self.device)
+                            for m in tree.device_maps(old.prim_perm, lay.prim_perm)))
         self.layout, self.arrays = lay, new_sa
+        self._set_tree(lay)
         self._upd = self._topology_state()  # leaf_of and dev_of of the new tree; the mirror is this scene's own already
         self._take_baseline(s)
         s.synchronize()
-        _lib.check(_lib.load().ptmi_scene_check(v), 'ptmi_scene_check')
         return maps
 
     def remap_ids(self, ids, maps, out=None, stream=None):
@@ -376,15 +292,15 @@ class DeviceScene:
         is out of range becomes -1. Returns a new tensor, or ``out`` (which may
         be ``ids`` itself). Asynchronous on ``stream``."""
         _check_tensor('ids', ids, ('H', 'W'), torch.int32, self.device)
-        counts = (self.layout.num_spheres, self.layout.num_triangles, self.layout.num_quads)
+        counts = counts_by_code(self.layout)
         maps = tuple(maps)
         if len(maps) != 3:
-            raise _lib.PtmiError('maps must be (spheres, triangles, quads)')
-        for m, n, name in zip(maps, counts, ('spheres', 'triangles', 'quads')):
+            raise _lib.PtmiError(f'maps must be ({", ".join(ByCode._fields)})')
+        for m, n, name in zip(maps, counts, ByCode._fields):
             _check_tensor(f'maps: {name}', m, (n,), torch.int32, self.device)
         with torch.cuda.device(self.device):
             if out is None:
-                with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.device)):
+                with torch.cuda.stream(_stream_or_current(stream, self.device)):
                     out = torch.empty_like(ids)
             _check_tensor('out', out, tuple(ids.shape), torch.int32, self.device)
             ptr = [m.data_ptr() if n else None for m, n in zip(maps, counts)]
@@ -395,20 +311,16 @@ class DeviceScene:
 
     def permute_rows(self, rows, maps, stream=None):
         """``primitive_rows()`` taken before a rebuild, in the device order after
-        it: row ``maps[t][k]`` of the result is row k of ``rows``. ``rows`` is
-        (spheres, quads, tris) as primitive_rows returns them, ``maps`` is
-        rebuild()'s (spheres, triangles, quads)."""
-        lay = self.layout
+        it, both ByStorage: row ``maps[t][k]`` of the result is row k of
+        ``rows``. ``maps`` is rebuild()'s ByCode."""
         out = []
-        with torch.cuda.device(self.device), torch.cuda.stream(
-                stream if stream is not None else torch.cuda.current_stream(self.device)):
-            for r, m, n, w in ((rows[0], maps[0], lay.num_spheres, 4), (rows[1], maps[2], lay.num_quads, 16),
-                               (rows[2], maps[1], lay.num_triangles, 12)):
-                new = r.clone()
+        with torch.cuda.device(self.device), torch.cuda.stream(_stream_or_current(stream, self.device)):
+            for k, r in zip(STORAGE, rows):
+                n, w, new = getattr(self.layout, k.count), k.row_floats, r.clone()
                 if n:
-                    new[:n * w].view(n, w)[m.long()] = r[:n * w].view(n, w)
+                    new[:n * w].view(n, w)[maps[k.code].long()] = r[:n * w].view(n, w)
                 out.append(new)
-        return tuple(out)
+        return ByStorage(*out)
 
 
 def make_frame(cam, bg, max_depth, seed, width, height, window=None, band=(1, 1, 0), traversal='stack'):
@@ -564,7 +476,7 @@ class Integrator:
           and work on the caller's stream after this call sees the resolved
           accumulator as usual."""
         dev = self.scene.device
-        caller = stream if stream is not None else torch.cuda.current_stream(dev)
+        caller = _stream_or_current(stream, dev)
         npix = frame.w * len(frame_pixel_rows(frame))
         if npix == 0 or sample_count <= 0:
             return
@@ -885,10 +797,10 @@ class Integrator:
             self._check_image('ids', ids_prev, h, w)
             rows = tuple(prev_rows)
             if len(rows) != 3:
-                raise _lib.PtmiError('prev_rows must be (spheres, quads, tris)')
-            for t, mine, name in zip(rows, (self.scene.t_spheres, self.scene.t_quads, self.scene.t_tris),
-                                     ('spheres', 'quads', 'tris')):
-                _check_tensor(f'prev_rows: {name}', t, tuple(mine.shape), torch.float32, self.scene.device)
+                raise _lib.PtmiError(f'prev_rows must be ({", ".join(ByStorage._fields)})')
+            for t, k, name in zip(rows, STORAGE, ByStorage._fields):
+                _check_tensor(f'prev_rows: {name}', t, tuple(getattr(self.scene, k.tensor).shape), torch.float32,
+                              self.scene.device)
         cur, prev = temporal.camera(cur_cam), temporal.camera(prev_cam)
         prm = motion.params(*prm, match_ids) if moved else temporal.params(*prm)
         with self._dev():
@@ -903,7 +815,7 @@ class Integrator:
             tail = (w, h, C.byref(prm), out_accum.data_ptr(), out_stats.data_ptr(), self._stream(stream))
             if moved:
                 _lib.check(lib.ptmi_reproject_moved(*head, ids_cur.data_ptr(), ids_prev.data_ptr(), self.scene.view,
-                                                    rows[0].data_ptr(), rows[1].data_ptr(), rows[2].data_ptr(), *tail),
+                                                    *(r.data_ptr() for r in rows), *tail),
                            'ptmi_reproject_moved')
             else:
                 _lib.check(lib.ptmi_reproject(*head, *tail), 'ptmi_reproject')
@@ -936,7 +848,7 @@ class Integrator:
 
     def reset_counters(self, stream=None):
         if self.counters is not None:
-            s = stream if stream is not None else torch.cuda.current_stream(self.scene.device)
+            s = _stream_or_current(stream, self.scene.device)
             self._after_traces(s)
             with torch.cuda.stream(s):
                 self.counters.zero_()

@@ -62,7 +62,7 @@ import numpy as np
 import torch
 
 from . import _lib, bvh as bvh_mod, core, device, scene_compiler, tree as tree_mod
-from .scene_data import SceneArrays
+from .scene_data import STORAGE, SceneArrays
 
 # kernels.py:746: the reference's switch between its front-to-back stack
 # traversal (False, its default) and its parent-pointer stackless traversal.
@@ -547,28 +547,26 @@ class MI355XRenderer:
     def _apply_update(self, spheres, quads, triangles):
         """update_primitives' checks and the update itself, up to the bumped
         ``scene_revision``; what becomes of the image is the caller's."""
-        kinds = {'spheres': ('Sphere', 'sphere_mats', lambda o: o.material, lambda o: o.center.at(0.0)),
-                 'quads': ('quad', 'quad_mats', lambda o: o.mat, lambda o: o.Q),
-                 'triangles': ('triangle', 'tri_mats', lambda o: o.mat, lambda o: o.v0)}
-        given = {'spheres': spheres or {}, 'quads': quads or {}, 'triangles': triangles or {}}
-        for name, new in given.items():
-            kind, mats_name, get_mat, get_ref = kinds[name]
-            mats, have = getattr(self.arrays, mats_name), self._prims[name]
+        getters = {'Sphere': (lambda o: o.material, lambda o: o.center.at(0.0)),  # the material, a reference point
+                   'quad': (lambda o: o.mat, lambda o: o.Q), 'triangle': (lambda o: o.mat, lambda o: o.v0)}
+        given = {k.name: new or {} for k, new in zip(STORAGE, (spheres, quads, triangles))}
+        for k in STORAGE:
+            name, kind, new, (get_mat, get_ref) = k.name, k.class_name, given[k.name], getters[k.class_name]
+            mats, have = getattr(self.arrays, k.materials), self._prims[name]
             for i, obj in new.items():
                 if not isinstance(i, (int, np.integer)) or not 0 <= i < len(have):
                     raise ValueError(f'{name}: no primitive {i!r} (the scene has {len(have)}); {self._REBUILD}')
                 if type(obj).__name__ != kind:
                     raise ValueError(f'{name}[{i}]: a {type(obj).__name__} cannot replace a {kind}; {self._REBUILD}')
                 row = scene_compiler._material_row(get_mat(obj), get_ref(obj), self._img_reg)
-                for k, v in row.items():
-                    if np.asarray(v, mats[k].dtype).tobytes() != mats[k][i].tobytes():
-                        raise ValueError(f'{name}[{i}]: the new object changes {k}; materials are fixed, '
+                for key, v in row.items():
+                    if np.asarray(v, mats[key].dtype).tobytes() != mats[key][i].tobytes():
+                        raise ValueError(f'{name}[{i}]: the new object changes {key}; materials are fixed, '
                                          f'{self._REBUILD}')
         order = {name: sorted(new) for name, new in given.items()}
-        records = scene_compiler.update_records(*([given[name][i] for i in order[name]]
-                                                  for name in ('spheres', 'quads', 'triangles')))
-        args = [(np.asarray(order[name], np.int64), rows, build) if order[name] else None
-                for name, (rows, build) in zip(('spheres', 'quads', 'triangles'), records)]
+        records = scene_compiler.update_records(*([given[k.name][i] for i in order[k.name]] for k in STORAGE))
+        args = [(np.asarray(order[k.name], np.int64), rows, build) if order[k.name] else None
+                for k, (rows, build) in zip(STORAGE, records)]
         torch.cuda.synchronize(self.dscene.device)  # no render of the scene in flight on any stream (overlapped traces)
         self.dscene.update_primitives(*args)
         for name, new in given.items():

@@ -21,7 +21,7 @@ from __future__ import annotations
 
 import numpy as np
 
-PRIM_SPHERE, PRIM_TRIANGLE, PRIM_QUAD = 0, 1, 2
+from .scene_data import PRIM_QUAD, PRIM_SPHERE, PRIM_TRIANGLE  # noqa: F401
 MAT_LAMBERTIAN, MAT_METAL, MAT_DIELECTRIC, MAT_EMISSIVE, MAT_ISOTROPIC = 0, 1, 2, 3, 4
 TEX_SOLID, TEX_CHECKER, TEX_IMAGE, TEX_NOISE = 0, 1, 2, 3
 

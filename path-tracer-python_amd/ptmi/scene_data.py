@@ -22,6 +22,40 @@ import numpy as np
 PRIM_SPHERE, PRIM_TRIANGLE, PRIM_QUAD = 0, 1, 2  # scene_compiler.py:10-12
 MAX_IMAGES = 16
 
+
+# What the host layer knows of one primitive kind: its name in the API (update_primitives' keyword, the renderer's
+# ``primitives`` key) and its type code (bvh_prim_type, leaf codes, ids); the f32 per device row (include/ptmi.h) and
+# per builder-form record ({c, r}; {v0, v1, v2}; {Q, u, v}) and the row columns such a record begins with; the
+# attributes it goes by: geometry, materials and count on SceneArrays (the count also on DeviceLayout and the scene
+# view), rows on DeviceLayout (and the view), tensor on DeviceScene; the class name the compiler and the renderer check.
+PrimKind = collections.namedtuple('PrimKind', 'name code row_floats build_floats build_columns geometry materials '
+                                              'count rows tensor class_name')
+# one value per kind, in the only two orders there are:
+ByCode = collections.namedtuple('ByCode', 'spheres triangles quads')  # prim_perm, row maps, leaf_of / dev_of, counts
+ByStorage = collections.namedtuple('ByStorage', 'spheres quads tris')  # primitive_rows(), permute_rows(), prev_rows
+
+# by type code; the columns are QUAD_COLUMNS' quad_Q .. quad_v and TRI_COLUMNS' triangle_v0 (below)
+KINDS = (PrimKind('spheres', PRIM_SPHERE, 4, 4, slice(0, 4), 'sphere_data', 'sphere_mats', 'num_spheres', 'spheres',
+                  't_spheres', 'Sphere'),
+         PrimKind('triangles', PRIM_TRIANGLE, 12, 9, slice(0, 3), 'tris', 'tri_mats', 'num_triangles', 'tris',
+                  't_tris', 'triangle'),
+         PrimKind('quads', PRIM_QUAD, 16, 9, slice(4, 13), 'quads', 'quad_mats', 'num_quads', 'quads', 't_quads',
+                  'quad'))
+# the order of the device tensors, of the blocks of ``mats`` and of update_primitives' arguments
+STORAGE = (KINDS[PRIM_SPHERE], KINDS[PRIM_QUAD], KINDS[PRIM_TRIANGLE])
+
+
+def counts_by_code(obj):
+    """ByCode of the primitive counts of a SceneArrays, a DeviceLayout or a scene view."""
+    return ByCode(*(int(getattr(obj, k.count)) for k in KINDS))
+
+
+def mat_bases(counts):
+    """ByCode of the first ``mats`` row of each kind, for ByCode ``counts``: the blocks lie in storage order."""
+    ends = np.cumsum([counts[k.code] for k in STORAGE])
+    return ByCode(**{k.name: int(end) - counts[k.code] for k, end in zip(STORAGE, ends)})
+
+
 # per-type material array names (compile_materials, scene_compiler.py:425-439)
 MAT_KEYS = ('material_type', 'material_albedo', 'material_fuzz', 'material_ir', 'material_emit_color',
             'texture_type', 'texture_scale', 'texture_color1', 'texture_color2', 'texture_image_idx',
@@ -77,7 +111,7 @@ class SceneArrays:
         return int(self.bvh['bvh_bbox_min'].shape[0])
 
     def mats(self, prim_type):
-        return {PRIM_SPHERE: self.sphere_mats, PRIM_TRIANGLE: self.tri_mats, PRIM_QUAD: self.quad_mats}[prim_type]
+        return getattr(self, KINDS[prim_type].materials)
 
     # ------------------------------------------------------------ constructors
     @classmethod
@@ -230,8 +264,7 @@ class DeviceLayout:
     num_spheres: int
     num_quads: int
     num_triangles: int
-    # device primitive k of type t is the reference's primitive prim_perm[t][k]
-    # (types indexed sphere 0, triangle 1, quad 2; identity unless leaf_order)
+    # a ByCode: device primitive k of type t is the reference's primitive prim_perm[t][k] (identity unless leaf_order)
     prim_perm: tuple = ()
     # the reference's own nodes for the stackless traversal (include/ptmi.h
     # ref_nodes): (num_bvh_nodes, 12) f32
@@ -304,7 +337,7 @@ def leaf_depths(bvh):
 
 
 def leaf_order_perm(bvh, counts):
-    """Per primitive type, the reference's primitive indices in the order the
+    """ByCode, for ByCode ``counts``, of the reference's primitive indices in the order the
     preorder flattened BVH reaches their leaves (index order is preorder,
     sah_bvh_builder.py:338-418). Laying the device primitives and materials
     out in this order puts primitives that share a subtree, and are therefore
@@ -320,7 +353,7 @@ def leaf_order_perm(bvh, counts):
         if order.shape[0] != n or (n and not np.array_equal(np.sort(order), np.arange(n))):
             raise ValueError(f'BVH leaves of type {t} are not a permutation of the {n} primitives')
         perm.append(order)
-    return tuple(perm)
+    return ByCode(*perm)
 
 
 def ref_layout_nodes(bvh, codes):
@@ -397,8 +430,6 @@ QUAD_COLUMNS = {'quad_normal': slice(0, 3), 'quad_D': 3, 'quad_Q': slice(4, 7), 
                 'quad_v': slice(10, 13), 'quad_w': slice(13, 16)}
 TRI_COLUMNS = {'triangle_v0': slice(0, 3), 'triangle_edge1': slice(3, 6), 'triangle_edge2': slice(6, 9),
                'triangle_normal': slice(9, 12)}
-# by primitive type code: the row columns that a builder-form record ({c, r}; {v0, v1, v2}; {Q, u, v}) begins with
-BUILD_COLUMNS = (slice(0, 4), TRI_COLUMNS['triangle_v0'], slice(4, 13))
 
 
 def _pack_rows(arrays, columns, width):
@@ -410,12 +441,12 @@ def _pack_rows(arrays, columns, width):
 
 def pack_quads(q):
     """Device rows (include/ptmi.h: 16 f32) of reference-layout quad arrays (QUAD_KEYS), in their order."""
-    return _pack_rows(q, QUAD_COLUMNS, 16)
+    return _pack_rows(q, QUAD_COLUMNS, KINDS[PRIM_QUAD].row_floats)
 
 
 def pack_tris(t):
     """Device rows (12 f32) of reference-layout triangle arrays (TRI_KEYS), in their order."""
-    return _pack_rows(t, TRI_COLUMNS, 12)
+    return _pack_rows(t, TRI_COLUMNS, KINDS[PRIM_TRIANGLE].row_floats)
 
 
 def unpack_quads(rows):
@@ -477,25 +508,16 @@ def pack_device(sa: SceneArrays, node_bytes: int = NODE_BYTES, leaf_order: bool 
     internal = np.nonzero(~is_leaf)[0]
     if np.any(left[internal] < 0) or np.any(right[internal] < 0):
         raise ValueError('internal BVH node with a missing child')
-    cidx = np.full(n, -1, np.int64)
-    cidx[internal] = np.arange(internal.shape[0])
-    counts = (ns, nt, nq)  # by prim type code: sphere 0, triangle 1, quad 2
-    if leaf_order and n:
-        perm = leaf_order_perm(b, counts)
-    else:
-        perm = tuple(np.arange(c, dtype=np.int64) for c in counts)
+    counts = counts_by_code(sa)
+    perm = leaf_order_perm(b, counts) if leaf_order and n else ByCode(*(np.arange(c, dtype=np.int64) for c in counts))
     new_idx = pidx.astype(np.int64).copy()
     for t in range(3):
-        inv = np.empty(counts[t], np.int64)
-        inv[perm[t]] = np.arange(counts[t])
         sel = is_leaf & (ptype == t)
-        new_idx[sel] = inv[pidx[sel]]
+        new_idx[sel] = np.argsort(perm[t])[pidx[sel]]  # the permutation's inverse
     if max(counts) > MAX_PRIMS_PER_TYPE:
         raise ValueError(f'at most {MAX_PRIMS_PER_TYPE} primitives of one type (25-bit leaf index)')
-    ps, pt, pq = perm
-    mats = np.concatenate([_pack_mats(sa.sphere_mats, ns)[ps], _pack_mats(sa.quad_mats, nq)[pq],
-                           _pack_mats(sa.tri_mats, nt)[pt]], axis=0)
-    mat_base = np.array([0, ns + nq, ns], np.int64)  # mats rows: spheres | quads | triangles, by type code
+    mats = np.concatenate([_pack_mats(sa.mats(k.code), counts[k.code])[perm[k.code]] for k in STORAGE], axis=0)
+    mat_base = np.array(mat_bases(counts), np.int64)
     cls = np.zeros(n, np.int64)
     if n:
         rows = mat_base[np.where(is_leaf, ptype, 0)] + np.where(is_leaf, new_idx, 0)
@@ -523,8 +545,8 @@ def pack_device(sa: SceneArrays, node_bytes: int = NODE_BYTES, leaf_order: bool 
     else:
         root_ref, root_min, root_max, max_leaf_depth = 0, np.zeros(3, np.float32), np.zeros(3, np.float32), 0
     shell = shell_hint(sa, cidx, max_leaf_depth, node_bytes)
-    spheres =np.ascontiguousarray(np.asarray(sa.sphere_data, np.float32).reshape(ns, 4)[ps])
-    quads, tris = pack_quads(sa.quads)[pq], pack_tris(sa.tris)[pt]
+    spheres = np.ascontiguousarray(np.asarray(sa.sphere_data, np.float32).reshape(ns, 4)[perm.spheres])
+    quads, tris = pack_quads(sa.quads)[perm.quads], pack_tris(sa.tris)[perm.triangles]
     if len(sa.images) > MAX_IMAGES:
         raise ValueError(f'at most {MAX_IMAGES} image textures')
     texels, offs, ws, hs, off = [], [], [], [], 0

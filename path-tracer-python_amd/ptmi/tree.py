@@ -16,6 +16,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from .scene_data import ByCode, KINDS
 
 TREE_VERSION = 1  # PTMI_TREE_VERSION of include/ptmi_tree.h
 GROWTH_LANES = 1024  # PTMI_TREE_GROWTH_LANES
@@ -33,8 +34,8 @@ REBUILD_GROWTH = 3.89
 
 
 class IdsCounts(C.Structure):
-    """ptmi_ids_counts: the primitive counts by type code (sphere 0, triangle 1, quad 2)."""
-    _fields_ = [('spheres', C.c_int32), ('triangles', C.c_int32), ('quads', C.c_int32)]
+    """ptmi_ids_counts: the primitive counts by type code."""
+    _fields_ = [(k.name, C.c_int32) for k in KINDS]
 
 
 def _signatures():
@@ -59,12 +60,7 @@ def load():
 
 
 def device_maps(old_perm, new_perm):
-    """Per primitive type code, the int32 map old device row -> new device row
-    of two ``DeviceLayout.prim_perm`` (device row -> reference index) of the
-    same primitives."""
-    maps = []
-    for old, new in zip(old_perm, new_perm):
-        inv = np.empty(len(new), np.int64)
-        inv[np.asarray(new, np.int64)] = np.arange(len(new))
-        maps.append(inv[np.asarray(old, np.int64)].astype(np.int32))
-    return tuple(maps)
+    """ByCode of the int32 maps old device row -> new device row of two ``DeviceLayout.prim_perm`` (device row ->
+    reference index) of the same primitives."""
+    return ByCode(*(np.argsort(np.asarray(new, np.int64))[np.asarray(old, np.int64)].astype(np.int32)
+                    for old, new in zip(old_perm, new_perm)))  # through the new permutation's inverse

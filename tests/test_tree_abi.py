@@ -272,6 +272,33 @@ def test_rebuilt_mirror_packs_to_the_layout_of_a_compile_of_the_edited_arrays(fr
         assert (old.max_leaf_depth, lay_rebuilt.max_leaf_depth) == (15, 16)
 
 
+@pytest.mark.parametrize('name,width', [('kernel_paths_materials', None), ('coverage', 64)])
+def test_index_maps_of_a_rebuilt_tree_follow_the_row_maps(name, width):
+    """The numpy half of DeviceScene.rebuild on scenes whose three counts differ: the index maps made anew for
+    the rebuilt tree agree with the reference and invert its prim_perm per kind, and device_maps, by field name,
+    carries every old device row to the new row of the same reference primitive."""
+    sa = ph.fixture(name, width)
+    counts = (sa.num_spheres, sa.num_triangles, sa.num_quads)
+    mirror = uh.refit(sa, th.mixed_edit(sa))
+    new_sa = th.rebuilt(mirror)
+    old, new = sd.pack_device(mirror), sd.pack_device(new_sa)
+    before = update.index_maps(mirror.bvh, old.prim_perm, counts)
+    after = update.index_maps(new_sa.bvh, new.prim_perm, counts)
+    maps = tree.device_maps(old.prim_perm, new.prim_perm)
+    assert maps._fields == ('spheres', 'triangles', 'quads') == old.prim_perm._fields
+    assert [m.shape for m in maps] == [(c,) for c in counts] and {m.dtype for m in maps} == {np.dtype(np.int32)}
+    for t, (kind, old_rows, new_rows) in enumerate((('spheres', old.spheres, new.spheres),
+                                                    ('triangles', old.tris, new.tris),
+                                                    ('quads', old.quads, new.quads))):
+        m = getattr(maps, kind)
+        assert m is maps[t] and np.array_equal(np.sort(m), np.arange(counts[t]))
+        assert np.array_equal(after['leaf_of'][t], uh.leaf_of(new_sa, t))
+        assert np.array_equal(new.prim_perm[t][after['dev_of'][t]], np.arange(counts[t]))
+        assert np.array_equal(after['dev_of'][t], m[before['dev_of'][t]])  # reference index -> old row -> new row
+        assert old_rows.tobytes() == new_rows[m].tobytes()
+    assert any(not np.array_equal(m, np.arange(len(m))) for m in maps)  # the edit did reorder some leaves
+
+
 def test_ids_remap_reference_on_hostile_ids():
     maps = [np.array([2, 0, 1, -1, 5], np.int32), np.array([1, 0], np.int32), np.zeros(0, np.int32)]
     S, T, Q = 0, 1 << 28, 2 << 28

@@ -151,6 +151,103 @@ def test_topology_orders_children_before_parents(name, width):
     assert len(level_end) == int(sd.leaf_depths(sa.bvh)[inner].max()) + 1
 
 
+# ------------------------------------------------------------------ the numpy halves of DeviceScene.update_primitives
+# every count differs (9 spheres, 7 quads, 5 triangles; 6, 9, 3002), so a swap of two kinds changes a shape or a byte
+HOST_SCENES = [('kernel_paths_materials', None), ('coverage', 64)]
+KIND_NAMES = {'spheres': 0, 'triangles': 1, 'quads': 2}  # the API name -> the type code, restated here
+
+
+@pytest.mark.parametrize('name,width', HOST_SCENES)
+def test_index_maps_agree_with_the_reference_and_invert_prim_perm(name, width):
+    sa = ph.fixture(name, width)
+    lay = sd.pack_device(sa)
+    counts = (sa.num_spheres, sa.num_triangles, sa.num_quads)
+    assert len(set(counts)) == 3 and min(counts) > 0
+    maps = update.index_maps(sa.bvh, lay.prim_perm, counts)
+    assert tuple(sd.counts_by_code(sa)) == counts == tuple(sd.counts_by_code(lay))
+    for kind, t in KIND_NAMES.items():
+        leaf_of, dev_of = getattr(maps['leaf_of'], kind), getattr(maps['dev_of'], kind)
+        assert leaf_of is maps['leaf_of'][t] and dev_of is maps['dev_of'][t]
+        assert leaf_of.dtype == dev_of.dtype == np.int64 and leaf_of.shape == dev_of.shape == (counts[t],)
+        assert np.array_equal(leaf_of, uh.leaf_of(sa, t))
+        assert np.array_equal(lay.prim_perm[t][dev_of], np.arange(counts[t]))  # the inverse, from both sides
+        assert np.array_equal(dev_of[lay.prim_perm[t]], np.arange(counts[t]))
+        assert lay.prim_perm[t] is getattr(lay.prim_perm, kind)
+    order, level_end, slot = update.topology(sa.bvh)
+    assert np.array_equal(maps['order'], order) and np.array_equal(maps['level_end'], level_end)
+    assert np.array_equal(maps['slot_np'], slot)
+    inner = np.nonzero(sa.bvh['bvh_prim_idx'] < 0)[0]
+    assert np.array_equal(maps['inner'], inner) and np.array_equal(maps['rows'], slot[inner])
+    assert np.array_equal(maps['left'], sa.bvh['bvh_left_child'][inner])
+    assert np.array_equal(maps['right'], sa.bvh['bvh_right_child'][inner])
+
+
+def test_check_edits_raises_every_error_with_its_message():
+    sa = ph.fixture('kernel_paths_materials')
+    counts = (sa.num_spheres, sa.num_triangles, sa.num_quads)
+    widths = {'spheres': (4, 4), 'quads': (16, 9), 'triangles': (12, 9)}
+
+    def bad(kind, message, idx=None, rows=None, build=None):
+        good = uh.current(sa, kind, [0, 2])
+        arg = tuple(g if v is None else v for g, v in zip(good, (idx, rows, build)))
+        with pytest.raises(ValueError, match='^' + re.escape(f'{kind}: {message}') + '$'):
+            update.check_edits(counts, **{kind: arg})
+
+    for kind, (nrow, nbuild) in widths.items():
+        n = counts[KIND_NAMES[kind]]
+        idx, rows, build = uh.current(sa, kind, [0, 2])
+        assert rows.shape == (2, nrow) and build.shape == (2, nbuild)
+        got = update.check_edits(counts, **{kind: (idx, rows, build)})
+        assert list(got) == [KIND_NAMES[kind]]
+        for a, b in zip(got[KIND_NAMES[kind]], (idx, rows, build)):
+            assert a.tobytes() == b.tobytes() and a.shape == b.shape
+        bad(kind, 'indices must be a 1-D integer array', idx=np.array([[0, 2]]))
+        bad(kind, 'indices must be a 1-D integer array', idx=np.array([0.0, 2.0]))
+        bad(kind, f'an index is outside [0, {n})', idx=np.array([0, n]))
+        bad(kind, f'an index is outside [0, {n})', idx=np.array([-1, 2]))
+        bad(kind, 'an index is repeated', idx=np.array([2, 2]))
+        shape = f'rows must be (n, {nrow}) and build records (n, {nbuild}) f32'
+        bad(kind, shape, rows=rows[:, :-1])
+        bad(kind, shape, build=build[:1])
+        bad(kind, shape, idx=np.array([0, 1, 2]))
+        for value in (np.nan, np.inf):
+            broken = rows.copy()
+            broken[1, -1] = value
+            bad(kind, 'rows and build records must be finite', rows=broken)
+            broken = build.copy()
+            broken[0, 0] = -value
+            bad(kind, 'rows and build records must be finite', build=broken)
+        moved = build.copy()
+        moved[1, 0] = np.nextafter(moved[1, 0], f32(np.inf))
+        bad(kind, 'a row and its build record name different points', build=moved)
+    # an edit the rows of another kind would fit is a shape error, not a silent swap
+    with pytest.raises(ValueError, match=re.escape('quads: rows must be (n, 16)')):
+        update.check_edits(counts, quads=uh.current(sa, 'triangles', [0]))
+    assert update.check_edits(counts) == {} == update.check_edits(counts, spheres=uh.current(sa, 'spheres', []))
+
+
+@pytest.mark.parametrize('name,width', HOST_SCENES)
+def test_refreshed_mirror_is_pack_device_of_the_refit_arrays(name, width):
+    """update.refresh_mirror, given the edits and the ref_nodes the device holds after them, leaves the mirror and
+    the layout byte for byte what update_helpers.refit and pack_device of its result give."""
+    sa = ph.fixture(name, width)
+    edits = {'spheres': uh.sphere_edit([1, 4], sa.sphere_data[[1, 4], 0:3] + f32(0.75), sa.sphere_data[[1, 4], 3]),
+             'quads': uh.quad_edit([0, 5], [((1.0, 2.0, 3.0), (4.0, 0.0, 0.0), (0.0, 0.0, 5.0)),
+                                            ((-2.0, 0.5, 1.0), (0.0, 1.5, 0.0), (0.25, 0.0, 1.0))]),
+             'triangles': uh.tri_edit([2], [((0.0, 0.0, 0.0), (9.0, 1.0, 0.0), (0.0, 7.0, 2.0))])}
+    want = uh.refit(sa, edits)
+    want_lay = sd.pack_device(want)
+    mirror, lay = uh.refit(sa), sd.pack_device(sa)  # copies of their own: the refresh writes in place
+    assert uh.arrays_equal(mirror, sa) and uh.layouts_equal(lay, want_lay)
+    maps = update.index_maps(mirror.bvh, lay.prim_perm, (sa.num_spheres, sa.num_triangles, sa.num_quads))
+    checked = update.check_edits((sa.num_spheres, sa.num_triangles, sa.num_quads), **edits)
+    assert sorted(checked) == [0, 1, 2]
+    update.refresh_mirror(mirror, lay, maps, checked, want_lay.ref_nodes.reshape(-1))
+    assert uh.layouts_equal(lay, want_lay) == [] and uh.arrays_equal(mirror, want)
+    assert all(np.array_equal(a, b) for a, b in zip(lay.prim_perm, want_lay.prim_perm))
+    assert not uh.arrays_equal(sa, want)  # and the fixture was not written
+
+
 def test_refit_form_by_tree_size():
     txt = header('ptmi_update.h')
     assert int(re.search(r'#define PTMI_UPDATE_ONE_GROUP (\d+)', txt).group(1)) == update.ONE_GROUP
@@ -255,3 +352,36 @@ def test_update_records_are_the_compilers_rows():
     bs, bq, bt = bvh.primitive_inputs(s, q, t)
     assert qb.tobytes() == bq.tobytes() and tb.tobytes() == bt.tobytes()
     assert qb.tobytes() == qr[:, 4:13].tobytes() and tb[:, 0:3].tobytes() == tr[:, 0:3].tobytes()
+
+
+def test_kind_table_is_consistent_with_the_compiler_and_the_packer():
+    """scene_data.KINDS against what the code makes of one object of each kind: update_records' row and build
+    widths, the build columns of a row against the head of its build record, and pack_device's array widths."""
+    from ptmi import core, scene_compiler as sc
+    mat = core.lambertian(core.solid_color(core.vec3(0.5, 0.5, 0.5)))
+    objs = {'spheres': core.Sphere.stationary(core.vec3(0.1, 0.2, 0.3), 0.7, mat),
+            'quads': core.quad(core.vec3(1, 2, 3), core.vec3(0.3, 0, 0.1), core.vec3(0, 0.7, 0), mat),
+            'triangles': core.triangle(core.vec3(0, 0, 0.1), core.vec3(1.1, 0, 0), core.vec3(0, 1.3, 0), mat)}
+    assert [k.code for k in sd.KINDS] == [0, 1, 2] == [sd.PRIM_SPHERE, sd.PRIM_TRIANGLE, sd.PRIM_QUAD]
+    assert [k.name for k in sd.KINDS] == list(sd.ByCode._fields) == ['spheres', 'triangles', 'quads']
+    assert [k.name for k in sd.STORAGE] == list(objs) and [k.rows for k in sd.STORAGE] == list(sd.ByStorage._fields)
+    assert all(k is sd.KINDS[k.code] for k in sd.STORAGE) and len({k.code for k in sd.STORAGE}) == 3
+    assert [k.tensor for k in sd.STORAGE] == ['t_spheres', 't_quads', 't_tris']
+    assert sc.PRIM_SPHERE is sd.PRIM_SPHERE and (sc.PRIM_TRIANGLE, sc.PRIM_QUAD) == (1, 2)
+    world = core.hittable_list()
+    for o in objs.values():
+        world.add(o)
+    sa = sd.compile_world(world)
+    lay = sd.pack_device(sa, leaf_order=False)
+    records = sc.update_records(*([o] for o in objs.values()))
+    for k, (rows, build) in zip(sd.STORAGE, records):
+        assert type(objs[k.name]).__name__ == k.class_name
+        assert rows.shape == (1, k.row_floats) and build.shape == (1, k.build_floats)
+        head = rows[:, k.build_columns]
+        assert head.shape[1] in (3, 4, 9) and head.tobytes() == build[:, :head.shape[1]].tobytes()
+        assert getattr(lay, k.rows).shape == (1, k.row_floats) and getattr(lay, k.rows).tobytes() == rows.tobytes()
+        assert getattr(sa, k.count) == getattr(lay, k.count) == 1 and sa.mats(k.code) is getattr(sa, k.materials)
+        geometry = getattr(sa, k.geometry)
+        assert geometry is {'spheres': sa.sphere_data, 'quads': sa.quads, 'triangles': sa.tris}[k.name]
+        assert update.check_edits((1, 1, 1), **{k.name: ([0], rows, build)})[k.code][1].shape == rows.shape
+    assert tuple(sd.mat_bases(sd.ByCode(spheres=9, triangles=5, quads=7))) == (0, 16, 9)  # spheres | quads | triangles
