@@ -1,6 +1,6 @@
 // pt_image.hpp — what the image kernels share (pt_denoise.hip,
-// pt_reproject.hip, the guide trace of pt_guide.hip, the flat kernels of
-// pt_abi.hip): a pixel between its float4 and its math-header form, the block
+// pt_reproject.hip, pt_validate.hip, the guide trace of pt_guide.hip, the flat
+// kernels of pt_abi.hip): a pixel between its float4 and its math-header form, the block
 // geometry of "one block per square tile on a 1-D grid", and the capped flat
 // grid of the grid-stride kernels.
 #pragma once

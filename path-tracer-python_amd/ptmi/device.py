@@ -15,7 +15,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib, bvh as bvh_mod, guide, motion, post, temporal, tree, update, wf_tiles
+from . import _lib, bvh as bvh_mod, guide, motion, post, temporal, tree, update, validate, wf_tiles
 from .scene_data import (BVH_KEYS, ByCode, ByStorage, DeviceLayout, STORAGE, SceneArrays, camera_upload,
                          counts_by_code, pack_device)
 
@@ -819,6 +819,40 @@ class Integrator:
                            'ptmi_reproject_moved')
             else:
                 _lib.check(lib.ptmi_reproject(*head, *tail), 'ptmi_reproject')
+        return out_accum, out_stats
+
+    # ------------------------------------------------ history validation (ptmi.validate)
+    def validate_history(self, hist_accum, hist_stats, fresh_accum, fresh_stats, *, radius=3, k_lo=2.0, k_hi=4.0,
+                         out=None, weight=None, stream=None):
+        """A carried history (``reproject``'s or ``reproject_moved``'s output)
+        validated against a stats render of the current scene from cleared
+        buffers and merged with it (ptmi_history_validate,
+        include/ptmi_validate.h): over a window of ``(2 radius + 1)^2`` pixels
+        the difference of the two mean luminances is set against its own
+        standard error; up to ``k_lo`` standard errors the history of the
+        window's pixel is kept, from ``k_hi`` on it is dropped, in between in
+        proportion. Returns (accum, stats) as new tensors, or the pair ``out``
+        if given (not one of the inputs); ``weight``, an (H, W) f32 tensor, if
+        given receives the kept fraction n_v / n_h of every pixel.
+        Asynchronous on ``stream``."""
+        lib = validate.load()
+        h, w = self._check_denoise_inputs(hist_accum, hist_stats)
+        self._check_image('accum', fresh_accum, h, w)
+        self._check_image('stats', fresh_stats, h, w)
+        prm = validate.params(radius, k_lo, k_hi)
+        with self._dev():
+            if out is None:
+                out = (torch.empty_like(hist_accum), torch.empty_like(hist_stats))
+            out_accum, out_stats = out
+            self._check_image('accum', out_accum, h, w)
+            self._check_image('stats', out_stats, h, w)
+            if weight is not None:
+                self._check_image('var', weight, h, w)
+            _lib.check(lib.ptmi_history_validate(hist_accum.data_ptr(), hist_stats.data_ptr(), fresh_accum.data_ptr(),
+                                                 fresh_stats.data_ptr(), w, h, C.byref(prm), out_accum.data_ptr(),
+                                                 out_stats.data_ptr(),
+                                                 weight.data_ptr() if weight is not None else None,
+                                                 self._stream(stream)), 'ptmi_history_validate')
         return out_accum, out_stats
 
     def _after_traces(self, stream):

@@ -24,6 +24,12 @@ the behaviour above, bit for bit.
 ``InteractiveViewer(..., temporal=True, motion=True)``: a scene update
 (``update_primitives``) keeps the history too, carried to where every surface
 point went. The default, motion=False, drops it as before.
+
+``InteractiveViewer(..., temporal=True, validate=True, validate_spp=4)``: after a
+reprojecting restart the first ``validate_spp`` samples are rendered apart and
+judge the carried history, which is dropped where the light has changed
+(``MI355XRenderer.render_validated``). The default,
+validate=False, leaves the accumulator bit for bit what it was.
 """
 from __future__ import annotations
 
@@ -62,9 +68,13 @@ def orbit_step(theta, phi, delta_x, delta_y, velocity=(0.3, 0.3)):
 
 class InteractiveViewer(MI355XRenderer):
     def __init__(self, world, cam, img_path: str, temporal: bool = False, max_history: float = 32,
-                 motion: bool = False, **kwargs):
+                 motion: bool = False, validate: bool = False, validate_spp: int = 4, **kwargs):
         if motion and not temporal:
             raise ValueError('motion=True keeps the temporal history across scene updates: it needs temporal=True')
+        if validate and not temporal:
+            raise ValueError('validate=True validates the temporal history after a restart: it needs temporal=True')
+        if int(validate_spp) < 2:
+            raise ValueError('validate_spp must be at least 2: one fresh sample has no variance to judge by')
         super().__init__(world, cam, img_path, **kwargs)
         # temporal=True: a camera move reprojects the accumulated history to the
         # new camera instead of clearing it (MI355XRenderer.reproject_history,
@@ -80,6 +90,10 @@ class InteractiveViewer(MI355XRenderer):
         self._history = None
         self.motion = bool(motion)
         self._history_kept = False  # the last restart reprojected: the next render keeps accum / stats
+        # validate=True: the first validate_spp samples after a reprojecting restart go through
+        # render_validated, which says how much of the history they kept
+        self.validate = bool(validate)
+        self.validate_spp = int(validate_spp)
         self.mouse_down = False
         self.last_mouse_x = 0
         self.last_mouse_y = 0
@@ -239,6 +253,7 @@ class InteractiveViewer(MI355XRenderer):
         self._upload_camera_to_gpu()
         t0 = time.time()
         stats_path = target_error is not None or self.temporal
+        validate_now = self.validate and self.temporal and self._history_kept
         if self.temporal and self._history_kept:
             # after a reprojecting restart: accum / stats hold the history, so the
             # warm-up sample goes to a scratch accumulator and nothing is cleared
@@ -263,6 +278,12 @@ class InteractiveViewer(MI355XRenderer):
         total_pixels = self.cam.img_width * self.cam.img_height
         print(f"\nRendering Progress:\n{'─' * 60}")
         self.render_start_time = time.time()
+        if validate_now and self.is_rendering_active and min(self.validate_spp, spp - self.current_sample) >= 2:
+            n = min(self.validate_spp, spp - self.current_sample)
+            kept = self.render_validated(n)
+            torch.cuda.synchronize(self.dscene.device)
+            print(f'{self.current_sample:4d}/{spp} validated the history: reprojected to '
+                  f'{100.0 * self.history_fraction:.1f}% of the pixels, {100.0 * kept:.1f}% of its samples kept')
         while self.is_rendering_active and self.current_sample < spp:
             n = min(display_interval - self.current_sample % display_interval, spp - self.current_sample)
             if self.current_sample == 0:

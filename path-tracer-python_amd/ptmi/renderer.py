@@ -51,6 +51,13 @@ the objects by the indices it takes. The image starts over. ``tree_growth()``
 says how far the refit tree's boxes have grown since it was built, and
 ``rebuild_bvh()`` / ``update_primitives(rebuild=True | 'auto')`` rebuild the
 BVH of the resident scene in place, history included.
+
+History validation (no counterpart in the reference): ``render_validated(spp)``
+renders a few fresh samples apart from the carried history, drops the history
+where a window of pixels says the light has changed (a moved shadow, a
+reflection) and merges the rest (DESIGN.md §21);
+InteractiveViewer(temporal=True, validate=True) does so after every
+reprojecting restart. Derived state: not checkpointed.
 """
 from __future__ import annotations
 
@@ -121,6 +128,10 @@ class MI355XRenderer:
         self.guide_trace_seconds = None
         # reproject_history(): the (accum, stats) pair it writes into next, swapped with the live pair on each call
         self._history_spare = None
+        # render_validated(): its fresh pair, its output pair (swapped with the live pair on each call) and the
+        # weight image, and the kept fraction of the history it last returned
+        self._validate_scratch = None
+        self.last_history_kept = None
         # update_primitives(): bumped on every scene update; part of the guides' cache key
         self.scene_revision = 0
         # rebuild_bvh() and update_primitives(rebuild=...): rebuilds done, and the (mean, max) growth 'auto' last read
@@ -638,6 +649,71 @@ class MI355XRenderer:
         self._tiles = self.integrator.new_tiles(self.frame)
         self._drop_denoised()
         return int((self.stats[..., 0] > 0).sum().item()) / (self.stats.shape[0] * self.stats.shape[1])
+
+    def render_validated(self, spp, integrator='megakernel', **params):
+        """Render ``spp`` fresh samples and let them judge the carried history
+        (Integrator.validate_history, include/ptmi_validate.h):
+        the call for the step after ``update_primitives(keep_history=True)``
+        or ``reproject_history``. The samples, from ``next_sample_index`` (a
+        viewer's) or ``current_sample`` on, go through the stats path of
+        ``integrator`` ('megakernel' or 'wavefront') into a cleared scratch
+        pair; ``accum`` and ``stats`` are validated against that pair and
+        merged with it into a second scratch pair, which is then swapped in.
+        Where a window of pixels says the light has changed, the history is
+        dropped and the pixel starts over from the fresh samples; elsewhere the
+        result is what rendering ``spp`` samples on top of the history gives,
+        up to the rounding of a merge of two Welford states. ``params`` are
+        ``radius``, ``k_lo`` and ``k_hi``.
+
+        ``current_sample`` advances by ``spp``, the tile states start over and
+        ``denoised`` is dropped. Returns the kept fraction of the history,
+        sum(n_v) / sum(n_h) over the image (1.0 where there was none), also
+        kept as ``last_history_kept``. Needs stats, and ``spp >= 2``: one
+        sample has no variance to judge by (ValueError). The scratch pairs are
+        the renderer's, made once per image size, apart from the spare pair of
+        ``reproject_history``. Derived state: not checkpointed. Single device,
+        whole frames."""
+        if integrator not in ('megakernel', 'wavefront'):
+            raise ValueError(f'unknown integrator {integrator!r}')
+        if self.stats is None:
+            raise ValueError('render_validated needs stats: render through the stats path (render_adaptive) first')
+        spp = int(spp)
+        if spp < 2:
+            raise ValueError('render_validated needs spp >= 2: a pixel with one fresh sample has no variance to '
+                             'judge its history by')
+        if self.frame.band_stride != 1:
+            raise ValueError('render_validated needs band_stride == 1 (banded frames are out of scope)')
+        integ = self.integrator
+        sc = self._validate_scratch
+        if sc is None or tuple(sc['fresh'][0].shape) != tuple(self.accum.shape):
+            pair = lambda: (torch.empty_like(self.accum), torch.empty_like(self.stats))  # noqa: E731
+            sc = self._validate_scratch = {'fresh': pair(), 'out': pair(),
+                                           'weight': torch.empty(tuple(self.stats.shape[:2]), dtype=torch.float32,
+                                                                 device=self.stats.device)}
+        fresh_accum, fresh_stats = sc['fresh']
+        integ.clear(self.frame, fresh_accum)
+        integ.clear_stats(self.frame, fresh_stats)
+        self._integrator_label = 'adaptive-' + integrator
+        begin = getattr(self, 'next_sample_index', self.current_sample)
+        t = time.time()
+        (integ.render_mk_stats if integrator == 'megakernel' else integ.render_wf_stats)(
+            self.frame, fresh_accum, fresh_stats, begin, spp)
+        hist = (self.accum, self.stats)
+        out = integ.validate_history(*hist, fresh_accum, fresh_stats, out=sc['out'], weight=sc['weight'], **params)
+        # sum(n_v) / sum(n_h): n_v = weight * n_h, whole numbers; a non-finite history pixel counts as empty
+        ok = torch.isfinite(hist[0]).all(-1) & torch.isfinite(hist[1][..., :3]).all(-1)
+        n_h = torch.where(ok, hist[1][..., 0], torch.zeros_like(sc['weight'])).double()
+        n_v = torch.round(sc['weight'].double() * n_h)
+        total, kept = float(n_h.sum().item()), float(n_v.sum().item())
+        self.accum, self.stats = out
+        sc['out'] = hist
+        dt = time.time() - t
+        self.sample_times += [dt / spp] * spp
+        self.current_sample += spp
+        self._tiles = integ.new_tiles(self.frame)
+        self._drop_denoised()
+        self.last_history_kept = kept / total if total > 0 else 1.0
+        return self.last_history_kept
 
     def denoise(self, iterations=5, sigma=4.0, guided=False, **guided_params):
         """Variance-guided a-trous filter of the accumulator by the per-pixel

@@ -1,0 +1,26 @@
+"""The parity and renderer cases of tests/test_gpu_validate.py with the
+register-budget stress build (libptmi_stress.so, see
+tests/test_gpu_stress_build.py): the stress library carries the history
+validation (its shipped object: the kernel is not register-capped), and
+render_validated's fresh samples come from render kernels capped to the 8-wave
+VGPR budget and must give the same bits. Runs in a child process (the library is
+loaded once per process)."""
+import os
+import subprocess
+import sys
+
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..')
+STRESS = os.path.join(ROOT, 'path-tracer-python_amd', 'ptmi', '_lib', 'libptmi_stress.so')
+
+
+def test_stress_build_parity_and_renderer_cases():
+    assert os.path.exists(STRESS), 'libptmi_stress.so missing: run __graft_entry__.build()'
+    p = subprocess.run([sys.executable, '-m', 'pytest', os.path.join(ROOT, 'tests', 'test_gpu_validate.py'), '-q', '-x',
+                        '-p', 'no:cacheprovider', '-k', 'test_kernel_equals_reference or test_render_validated'],
+                       env=dict(os.environ, PTMI_LIB=STRESS), capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-2000:]
+    assert '19 passed' in p.stdout and 'skipped' not in p.stdout, p.stdout[-2000:]
