@@ -23,4 +23,4 @@ def test_stress_build_parity_and_renderer_cases():
                         '-p', 'no:cacheprovider', '-k', 'test_kernel_equals_reference or test_render_validated'],
                        env=dict(os.environ, PTMI_LIB=STRESS), capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-2000:]
-    assert '19 passed' in p.stdout and 'skipped' not in p.stdout, p.stdout[-2000:]
+    assert '22 passed' in p.stdout and 'skipped' not in p.stdout, p.stdout[-2000:]

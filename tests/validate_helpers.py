@@ -15,7 +15,9 @@ import reproject_helpers as rh
 
 f32 = np.float32
 DEFAULTS = dict(radius=3, k_lo=2.0, k_hi=4.0)
-FRAMES = [(48, 27), (37, 21), (16, 16), (17, 1), (5, 3)]  # (width, height); 5 x 3 is smaller than any window but r = 0
+# (width, height); 5 x 3 is smaller than any window but r = 0; 80 x 50 is 5 x 4 tiles of 16 x 16 with a ragged bottom
+# row, the one frame with tiles (row 1, columns 1 - 3) whose halo of the largest radius lies wholly inside the image
+FRAMES = [(48, 27), (37, 21), (16, 16), (17, 1), (5, 3), (80, 50)]
 RADII = [0, 3, 7]
 
 
