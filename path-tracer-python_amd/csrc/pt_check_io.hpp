@@ -1,6 +1,6 @@
 // pt_check_io.hpp — the raw little-endian f32 files of the CPU check programs
 // (denoise_check.cpp, reproject_check.cpp, update_check.cpp, motion_check.cpp,
-// tree_check.cpp, validate_check.cpp).
+// tree_check.cpp, validate_check.cpp, material_check.cpp).
 // Host only.
 #pragma once
 #include <stdint.h>

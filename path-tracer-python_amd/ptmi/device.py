@@ -15,8 +15,8 @@ import os
 import numpy as np
 import torch
 
-from . import _lib, bvh as bvh_mod, guide, motion, post, temporal, tree, update, validate, wf_tiles
-from .scene_data import (BVH_KEYS, ByCode, ByStorage, DeviceLayout, STORAGE, SceneArrays, camera_upload,
+from . import _lib, bvh as bvh_mod, guide, material, motion, post, temporal, tree, update, validate, wf_tiles
+from .scene_data import (BVH_KEYS, ByCode, ByStorage, DeviceLayout, KINDS, STORAGE, SceneArrays, camera_upload,
                          counts_by_code, pack_device)
 
 
@@ -127,12 +127,14 @@ class DeviceScene:
                                  'primitive indices and keeps the arrays equal to the device)')
         if self.t_ref_nodes is None:
             raise _lib.PtmiError('update_primitives needs the scene\'s ref_nodes')
-        # the mirror: the geometry and the boxes are copied, so the caller's arrays stay as they were
+        # the mirror: the geometry, the materials and the boxes are copied, so the caller's arrays stay as they were
         b = dict(sa.bvh, bvh_bbox_min=sa.bvh['bvh_bbox_min'].copy(), bvh_bbox_max=sa.bvh['bvh_bbox_max'].copy())
         self.arrays = sa = dataclasses.replace(sa, sphere_data=sa.sphere_data.copy(), bvh=b,
                                                quads={k: v.copy() for k, v in sa.quads.items()},
-                                               tris={k: v.copy() for k, v in sa.tris.items()})
-        for name in ('nodes', 'spheres', 'quads', 'tris', 'ref_nodes', 'root_min', 'root_max'):
+                                               tris={k: v.copy() for k, v in sa.tris.items()},
+                                               **{k.materials: {key: v.copy() for key, v in sa.mats(k.code).items()}
+                                                  for k in KINDS})
+        for name in ('nodes', 'spheres', 'quads', 'tris', 'mats', 'ref_nodes', 'root_min', 'root_max'):
             setattr(lay, name, np.array(getattr(lay, name)))  # the layout is refreshed in place: its own copy
         self._tree_state()  # the growth baseline is the tree as built: taken before the first update moves a box
         self._upd = self._topology_state()
@@ -179,8 +181,9 @@ class DeviceScene:
         reference-layout mirror) and ``layout`` equal what the device holds,
         the view's root box is refreshed and its shell hint re-evaluated
         (scene_data.find_shell on the mirror; 0 if the claim no longer holds).
-        Topology, materials and counts do not change: for anything else build a
-        new DeviceScene. ``flags`` as for update_call (same bits either way)."""
+        Topology, materials and counts do not change: materials are
+        update_materials', for anything else build a new DeviceScene. ``flags``
+        as for update_call (same bits either way)."""
         st = self._update_state()
         edits = update.check_edits(counts_by_code(self.layout), spheres, quads, triangles)
         self._upload_edits(st, edits, stream, flags)
@@ -204,6 +207,60 @@ class DeviceScene:
             pi, pf = ti.data_ptr(), tf.data_ptr()
             lists = {t: (pi + 4 * a, pi + 4 * b, pf + 4 * c, pf + 4 * d, n) for t, (a, b, c, d, n) in lists.items()}
         self.update_call(lists, stream, flags)
+
+    # ------------------------------------------------ material edits (ptmi.material)
+    def material_call(self, lists, stream=None):
+        """ptmi_update_materials on this scene: ``lists`` maps a primitive type
+        code to (prim ptr, leaf ptr, row ptr, count) of edits already on the
+        device. Asynchronous; the host mirror and the view are not refreshed
+        (update_materials does both)."""
+        st = self._update_state()
+        arg = [C.byref(material.MaterialList(*e)) if e is not None and e[3] else None
+               for e in (lists.get(k.code) for k in STORAGE)]
+        with torch.cuda.device(self.device):
+            _lib.check(material.load().ptmi_update_materials(self.view, arg[0], arg[1], arg[2],
+                                                             st['slot'].data_ptr() if st['slot'] is not None else None,
+                                                             _stream_ptr(stream, self.device)),
+                       'ptmi_update_materials')
+
+    def update_materials(self, spheres=None, quads=None, triangles=None, stream=None):
+        """Replace material rows of the resident scene on the device
+        (include/ptmi_material.h). Each argument is ``(reference
+        primitive indices, rows)``: numpy arrays of n indices and (n, 20) f32
+        ``mats`` rows as include/ptmi.h lays them out, the flags word last.
+        Indices out of range or repeated, rows of another shape or with
+        non-finite values, and a flags word that names an image the scene does
+        not have are a ValueError before anything is uploaded. No render of
+        this scene may be in flight on another stream. On return the device is
+        updated: the rows, and the material class in both copies of each edited
+        primitive's leaf code. ``arrays`` (the reference-layout mirror, whose
+        material arrays are the scene's own copies) and ``layout`` equal what
+        the device holds: ``layout`` is pack_device of the edited arrays on the
+        same BVH, byte for byte. The view's root ref is refreshed (a
+        one-primitive scene's root is a leaf) and its shell hint re-evaluated:
+        a shell sphere that stops being a medium clears it, an enclosing
+        sphere that becomes one may gain it. Geometry, counts, topology, texels
+        and the growth baseline do not change."""
+        st = self._update_state()
+        edits = material.check_edits(counts_by_code(self.layout), len(self.layout.img_w), spheres, quads, triangles)
+        s = _stream_or_current(stream, self.device)
+        ints, floats, lists, ni, nf = [], [], {}, 0, 0
+        for t, (idx, rows) in edits.items():
+            n = idx.size
+            ints += [st['dev_of'][t][idx].astype(np.int32), st['leaf_of'][t][idx].astype(np.int32)]
+            floats.append(rows.reshape(-1))
+            lists[t] = (ni, ni + n, nf, n)  # element offsets, made pointers below
+            ni, nf = ni + 2 * n, nf + rows.size
+        if ints:
+            with torch.cuda.device(self.device), torch.cuda.stream(s):  # the uploads precede the kernel on its stream
+                ti = torch.from_numpy(np.concatenate(ints)).to(self.device)
+                tf = torch.from_numpy(np.concatenate(floats)).to(self.device)
+            pi, pf = ti.data_ptr(), tf.data_ptr()
+            lists = {t: (pi + 4 * a, pi + 4 * b, pf + 4 * c, n) for t, (a, b, c, n) in lists.items()}
+        self.material_call(lists, s)
+        s.synchronize()
+        material.refresh_mirror(self.arrays, self.layout, st, edits, self._pack[0])
+        self._set_tree(self.layout)
 
     # ------------------------------------------------ tree quality, rebuild in place (ptmi.tree)
     def _tree_state(self):

@@ -173,6 +173,13 @@ class InteractiveViewer(MI355XRenderer):
             return self._rebuild_scene() if self._wants_rebuild(rebuild, threshold) else None
         return self._change_scene(change, 'Scene updated')
 
+    def update_materials(self, spheres=None, quads=None, triangles=None, media=None):
+        """MI355XRenderer.update_materials. What becomes of the
+        temporal history is ``_change_scene``'s rule."""
+        def change():
+            self._apply_materials(spheres, quads, triangles, media)
+        return self._change_scene(change, 'Materials updated')
+
     def rebuild_bvh(self):
         """MI355XRenderer.rebuild_bvh, the temporal history treated as by ``update_primitives``."""
         return self._change_scene(self._rebuild_scene, 'BVH rebuilt')

@@ -51,6 +51,9 @@ the objects by the indices it takes. The image starts over. ``tree_growth()``
 says how far the refit tree's boxes have grown since it was built, and
 ``rebuild_bvh()`` / ``update_primitives(rebuild=True | 'auto')`` rebuild the
 BVH of the resident scene in place, history included.
+``update_materials`` replaces materials of the resident scene: a dimmed light,
+a recoloured wall, a diffuse ball turned to glass, a thicker fog (DESIGN.md
+§22).
 
 History validation (no counterpart in the reference): ``render_validated(spp)``
 renders a few fresh samples apart from the carried history, drops the history
@@ -61,6 +64,7 @@ reprojecting restart. Derived state: not checkpointed.
 """
 from __future__ import annotations
 
+import copy
 import dataclasses
 import os
 import time
@@ -429,9 +433,10 @@ class MI355XRenderer:
         in ``compile_scene``'s sphere, quad or triangle list) to the new
         ``Sphere`` / ``quad`` / ``triangle`` object. Only geometry changes:
         the object must be of the list's kind and compile to the material
-        record the primitive has; counts, order, media and the BVH topology
-        stay (a refit tree traverses slower the further objects scatter).
-        Anything else is a ValueError: that path is a new renderer.
+        record the primitive has (a new material is ``update_materials``');
+        counts, order, media and the BVH topology stay (a refit tree traverses
+        slower the further objects scatter). Anything else is a ValueError:
+        that path is a new renderer.
 
         The image starts over: the accumulator is cleared, the adaptive state
         is reset as for a new adaptive render, ``denoised`` and the
@@ -555,6 +560,95 @@ class MI355XRenderer:
         history = self._take_history(keep_history, params)
         return self._after_scene_change(history, self._rebuild_scene(), params)
 
+    # ------------------------------------------------------------ material edits
+    _MATERIAL_KINDS = ('lambertian', 'metal', 'dielectric', 'diffuse_light')
+    # per primitive class: the attribute that holds its material, and a reference point (scene_compiler's)
+    _PRIM_PARTS = {'Sphere': ('material', lambda o: o.center.at(0.0)), 'quad': ('mat', lambda o: o.Q),
+                   'triangle': ('mat', lambda o: o.v0)}
+
+    def update_materials(self, spheres=None, quads=None, triangles=None, media=None, keep_history=False, **params):
+        """Edit materials of the resident scene on the device
+        (DeviceScene.update_materials, include/ptmi_material.h)
+        instead of building a new renderer. ``spheres``, ``quads`` and
+        ``triangles`` map a reference primitive index (as in ``primitives``) to
+        the primitive's new material object: a ``lambertian`` (solid, checker,
+        noise or image texture), ``metal``, ``dielectric`` or
+        ``diffuse_light``. Its record is the scene compiler's own, so the
+        material arrays are afterwards those of a full compile of the edited
+        world. An ``image_texture`` must be one the scene was compiled with
+        (its texels are resident); any other is a ValueError that names the
+        rebuild path. ``primitives`` then holds copies of the objects with the
+        new materials.
+
+        Whether a primitive is the boundary of a constant medium is fixed, and
+        its medium fields are kept. ``media`` maps ``(kind, index)``, e.g.
+        ``('spheres', 3)``, of a primitive that is such a boundary to
+        ``(density, albedo)``, the medium's new density and the new albedo of
+        its phase function (three floats); for any other primitive it is a
+        ValueError. Counts, geometry and the BVH do not change.
+
+        The image is treated as by ``update_primitives``: by default it starts
+        over and the guides are retraced on their next use. With
+        ``keep_history=True`` (a stats render is needed) it is reprojected
+        through ``reproject_history`` with ``params``: the primitives have not
+        moved, and a surface whose guide albedo changed by more than
+        ``sigma_a`` loses its history there. The light that an edit changes on
+        other surfaces (a dimmed lamp, a recoloured wall's bounce) lags in the
+        kept history until ``render_validated`` has judged it.
+        Returns the fraction of pixels with history (None without
+        keep_history)."""
+        history = self._take_history(keep_history, params)
+        self._apply_materials(spheres, quads, triangles, media)
+        return self._after_scene_change(history, None, params)
+
+    def _apply_materials(self, spheres, quads, triangles, media):
+        """update_materials' checks and the edit itself, up to the bumped
+        ``scene_revision``; what becomes of the image is the caller's."""
+        given = {k.name: dict(new or {}) for k, new in zip(STORAGE, (spheres, quads, triangles))}
+        media = dict(media or {})
+        for key in media:
+            if not (isinstance(key, tuple) and len(key) == 2 and key[0] in given):
+                raise ValueError(f'media: {key!r} is not (kind, index) with kind one of {sorted(given)}')
+        args, objects = [], {}
+        for k in STORAGE:
+            name, have, mats = k.name, self._prims[k.name], getattr(self.arrays, k.materials)
+            attr, get_ref = self._PRIM_PARTS[k.class_name]
+            fog = {i: v for (kind, i), v in media.items() if kind == name}
+            records, order = [], sorted(set(given[name]) | set(fog))
+            for i in order:
+                if not isinstance(i, (int, np.integer)) or not 0 <= i < len(have):
+                    raise ValueError(f'{name}: no primitive {i!r} (the scene has {len(have)}); {self._REBUILD}')
+                rec = {key: mats[key][i] for key in mats}  # the current record; the medium fields stay
+                if i in given[name]:
+                    mat = given[name][i]
+                    if type(mat).__name__ not in self._MATERIAL_KINDS:
+                        raise ValueError(f'{name}[{i}]: {type(mat).__name__} is not a material '
+                                         f'({", ".join(self._MATERIAL_KINDS)})')
+                    tex = getattr(mat, 'tex', None)
+                    if type(tex).__name__ == 'image_texture' and id(tex) not in self._img_reg:
+                        raise ValueError(f'{name}[{i}]: the image texture is not one the scene was compiled with, '
+                                         f'so its texels are not resident; {self._REBUILD}')
+                    rec.update(scene_compiler._material_row(mat, get_ref(have[i]), self._img_reg))
+                    objects[name, i] = copy.copy(have[i])
+                    setattr(objects[name, i], attr, mat)
+                if i in fog:
+                    if not rec['is_constant_medium']:
+                        raise ValueError(f'media: {name}[{i}] is not the boundary of a constant medium; which '
+                                         f'primitives are is fixed, {self._REBUILD}')
+                    density, albedo = fog[i]
+                    albedo = [albedo.x, albedo.y, albedo.z] if hasattr(albedo, 'x') else [float(c) for c in albedo]
+                    if len(albedo) != 3:
+                        raise ValueError(f'media: {name}[{i}]: the albedo must be three floats')
+                    rec.update(medium_density=float(density), medium_albedo=albedo)
+                records.append(rec)
+            args.append((np.asarray(order, np.int64), scene_compiler.material_rows(records)) if order else None)
+        torch.cuda.synchronize(self.dscene.device)  # no render of the scene in flight on any stream (overlapped traces)
+        self.dscene.update_materials(*args)
+        for (name, i), obj in objects.items():
+            self._prims[name][i] = obj
+        self.arrays = self.dscene.arrays
+        self.scene_revision += 1
+
     def _apply_update(self, spheres, quads, triangles):
         """update_primitives' checks and the update itself, up to the bumped
         ``scene_revision``; what becomes of the image is the caller's."""
@@ -572,8 +666,8 @@ class MI355XRenderer:
                 row = scene_compiler._material_row(get_mat(obj), get_ref(obj), self._img_reg)
                 for key, v in row.items():
                     if np.asarray(v, mats[key].dtype).tobytes() != mats[key][i].tobytes():
-                        raise ValueError(f'{name}[{i}]: the new object changes {key}; materials are fixed, '
-                                         f'{self._REBUILD}')
+                        raise ValueError(f'{name}[{i}]: the new object changes {key}; materials are '
+                                         f'update_materials\' to edit, {self._REBUILD}')
         order = {name: sorted(new) for name, new in given.items()}
         records = scene_compiler.update_records(*([given[k.name][i] for i in order[k.name]] for k in STORAGE))
         args = [(np.asarray(order[k.name], np.int64), rows, build) if order[k.name] else None

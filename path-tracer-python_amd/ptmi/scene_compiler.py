@@ -295,6 +295,20 @@ def update_records(spheres=(), quads=(), triangles=()):
             (scene_data.pack_tris(compile_triangle_geometry(triangles)), tr))
 
 
+def material_rows(records):
+    """(n, 20) f32 ``mats`` rows (include/ptmi.h) of material records, dicts of
+    MAT_KEYS values as ``_material_row`` makes them plus the three medium
+    fields, for a material edit (DeviceScene.update_materials): each value goes
+    through the typed array compile_materials stores it in, so an edited
+    scene's material arrays equal those of a full compile of the edited world."""
+    from . import scene_data
+    m = scene_data._empty_mats(len(records))
+    for i, rec in enumerate(records):
+        for k, v in rec.items():
+            m[k][i] = v
+    return scene_data._pack_mats(m, len(records))
+
+
 def image_u8(tex):
     """RGB8 payload of an image texture: ptmi.core stores it; the reference's
     rtw_image keeps fdata = u8/255 (f32), inverted exactly by rounding."""

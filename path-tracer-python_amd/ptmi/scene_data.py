@@ -289,17 +289,32 @@ class DeviceLayout:
                    if a is not None) + (0 if self.ref_nodes is None else int(self.ref_nodes.nbytes))
 
 
+# f32 columns of a mats row (include/ptmi.h) per reference-layout array; f32 19 is the flags word
+MAT_FLOATS = 20
+MAT_COLUMNS = {'material_albedo': slice(0, 3), 'material_fuzz': 3, 'material_emit_color': slice(4, 7),
+               'material_ir': 7, 'texture_color1': slice(8, 11), 'texture_scale': 11,
+               'texture_color2': slice(12, 15), 'medium_density': 15, 'medium_albedo': slice(16, 19)}
+
+
+def mat_flags(rows):
+    """The flags words (uint32) of (n, 20) f32 mats rows."""
+    return np.ascontiguousarray(np.asarray(rows, np.float32)[:, MAT_FLOATS - 1]).view(np.uint32)
+
+
+def unpack_mats(rows):
+    """_pack_mats' inverse: the reference-layout material arrays (MAT_KEYS) of (n, 20) mats rows."""
+    flags = mat_flags(rows).astype(np.int64)
+    out = {key: rows[:, cols] for key, cols in MAT_COLUMNS.items()}
+    out.update(material_type=(flags & 0xf).astype(np.int32), texture_type=((flags >> 4) & 0xf).astype(np.int32),
+               is_constant_medium=((flags >> 8) & 1).astype(np.int32),
+               texture_image_idx=((flags >> 16) - 1).astype(np.int32))
+    return out
+
+
 def _pack_mats(m, n):
-    out = np.zeros((n, 20), np.float32)
-    out[:, 0:3] = m['material_albedo']
-    out[:, 3] = m['material_fuzz']
-    out[:, 4:7] = m['material_emit_color']
-    out[:, 7] = m['material_ir']
-    out[:, 8:11] = m['texture_color1']
-    out[:, 11] = m['texture_scale']
-    out[:, 12:15] = m['texture_color2']
-    out[:, 15] = m['medium_density']
-    out[:, 16:19] = m['medium_albedo']
+    out = np.zeros((n, MAT_FLOATS), np.float32)
+    for key, cols in MAT_COLUMNS.items():
+        out[:, cols] = m[key]
     mt = m['material_type'].astype(np.int64)
     tt = m['texture_type'].astype(np.int64)
     if n and (mt.min() < 0 or mt.max() > 15 or tt.min() < 0 or tt.max() > 15):
