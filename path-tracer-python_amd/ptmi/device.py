@@ -15,9 +15,9 @@ import os
 import numpy as np
 import torch
 
-from . import _lib, bvh as bvh_mod, guide, material, motion, post, temporal, tree, update, validate, wf_tiles
+from . import _lib, build as build_mod, bvh as bvh_mod, guide, material, motion, post, temporal, tree, update, validate, wf_tiles
 from .scene_data import (BVH_KEYS, ByCode, ByStorage, DeviceLayout, KINDS, STORAGE, SceneArrays, camera_upload,
-                         counts_by_code, pack_device)
+                         counts_by_code, node_slots, pack_device, shell_hint)
 
 
 def _stream_or_current(stream, device=None):
@@ -54,6 +54,8 @@ class DeviceScene:
         self._upd = None  # update_primitives' topology, index maps and root box, made by its first call
         self._tree = None  # tree_growth's baseline areas and result slot, made by its first call
         self._pack = (node_bytes, leaf_order)  # rebuild packs as the scene was packed
+        self._builder = None  # rebuild(builder='device')'s device buffers, made by its first call
+        self.last_rebuild = None  # {'builder': 'host' | 'device', 'reason': ...} of the last rebuild
         dev = torch.device(device if device is not None else 'cuda')
         if dev.type != 'cuda':
             raise _lib.PtmiError(f'DeviceScene needs a cuda device, got {dev}')
@@ -296,7 +298,7 @@ class DeviceScene:
             out = st['out'].cpu().numpy()
         return float(out[0]), float(out[1])
 
-    def rebuild(self, stream=None):
+    def rebuild(self, stream=None, builder='host'):
         """Rebuild the BVH of the resident scene in place: the
         native SAH builder on the mirror's builder-form arrays, pack_device of
         the mirror with the new BVH, and its nodes, ref_nodes, spheres, quads,
@@ -314,10 +316,31 @@ class DeviceScene:
         Returns a ByCode ``(spheres, triangles, quads)`` of int32 device
         tensors mapping each old device row to its new device row. Reference
         primitive indices (update_primitives' arguments) do not change; device
-        rows, and so the ids of trace_guides_ids, do."""
+        rows, and so the ids of trace_guides_ids, do.
+
+        ``builder='device'`` (include/ptmi_build.h) builds and
+        packs on the device instead: the mirror's builder-form records and the
+        old index maps are uploaded, ptmi_build_sah_device and ptmi_build_pack
+        run on ``stream``, and the status, the seven arrays, the maps and the
+        packed tensors are read back for ``arrays.bvh`` and ``layout``. What
+        the device, ``layout`` and the returned maps hold is byte for byte what
+        the host path leaves. A scene above ``build.MAX_PRIMS`` primitives
+        (decided before any launch), a scene packed in compile order and a
+        build that ends with PTMI_BUILD_NEEDS_HOST take the host path;
+        ``last_rebuild`` = {'builder': 'host' | 'device', 'reason': ...} says
+        which path ran and why."""
+        if builder not in ('host', 'device'):
+            raise ValueError(f"builder must be 'host' or 'device', not {builder!r}")
         self._update_state()  # the mirror (and the check that the scene was made from SceneArrays)
-        sa, old = self.arrays, self.layout
         s = _stream_or_current(stream, self.device)
+        reason = 'asked for'
+        if builder == 'device':
+            maps, reason = self._rebuild_device(s)
+            if maps is not None:
+                self.last_rebuild = {'builder': 'device', 'reason': reason}
+                return maps
+        self.last_rebuild = {'builder': 'host', 'reason': reason}
+        sa, old = self.arrays, self.layout
         q, t = sa.quads, sa.tris
         built = bvh_mod.build_sah(sa.sphere_data, np.concatenate([q['quad_Q'], q['quad_u'], q['quad_v']], axis=1),
                                   np.concatenate([t['triangle_v0'], t['triangle_v1'], t['triangle_v2']], axis=1))
@@ -335,12 +358,52 @@ class DeviceScene:
                     dst[:a.size].copy_(torch.from_numpy(np.ascontiguousarray(a).reshape(-1)))
             maps = ByCode(*(torch.from_numpy(m).to(self.device)
                             for m in tree.device_maps(old.prim_perm, lay.prim_perm)))
+        self._adopt_tree(lay, new_sa, s)
+        return maps
+
+    def _adopt_tree(self, lay, new_sa, s):
+        """After a rebuild on either path: the new layout and mirror, the view, the update topology, the baseline."""
         self.layout, self.arrays = lay, new_sa
         self._set_tree(lay)
         self._upd = self._topology_state()  # leaf_of and dev_of of the new tree; the mirror is this scene's own already
         self._take_baseline(s)
         s.synchronize()
-        return maps
+
+    def _rebuild_device(self, s):
+        """The device path of ``rebuild``: (maps, reason), or (None, why the host path has to run)."""
+        sa, old = self.arrays, self.layout
+        counts = counts_by_code(old)
+        n = sum(counts)
+        if n > build_mod.MAX_PRIMS:
+            return None, f'{n} primitives, the device builder takes {build_mod.MAX_PRIMS}'
+        if n == 0 or not self._pack[1]:
+            return None, 'an empty scene' if n == 0 else 'the scene is packed in compile order'
+        if self._builder is None:
+            self._builder = build_mod.DeviceBuilder(counts, self.device)
+        b = self._builder
+        sp = _stream_ptr(s, self.device)
+        with torch.cuda.device(self.device), torch.cuda.stream(s):
+            b.upload(build_mod.builder_records(sa), self._upd['dev_of'])
+            b.build(sp)
+            b.pack(self.view, sp)
+            ints, status, info, new_row, perm = b.read_ints()  # the copy waits for both kernels
+            if int(status[0]) == build_mod.NEEDS_HOST:
+                return None, 'PTMI_BUILD_NEEDS_HOST: a fallback segment the device does not sort'
+            if int(status[0]) != 0 or int(info[10]) != 0:
+                raise _lib.PtmiError(f'device rebuild: status {int(status[0])}, pack status {int(info[10])}')
+            bmin, bmax = b.read_boxes()
+            tensors = {'nodes': self.t_nodes, 'ref_nodes': self.t_ref_nodes, 'mats': self.t_mats}
+            tensors.update({k.rows: getattr(self, k.tensor) for k in STORAGE})
+            tensors = {k: t.cpu().numpy() for k, t in tensors.items()}
+            a = int(b.i_off[10])
+            maps = ByCode(*(b.ti[a + sum(counts[:t]):a + sum(counts[:t + 1])].clone() for t in range(3)))
+        bvh = dict({k: v.copy() for k, v in ints.items()}, bvh_bbox_min=bmin.copy(), bvh_bbox_max=bmax.copy())
+        new_sa = dataclasses.replace(sa, bvh={k: bvh[k] for k in BVH_KEYS})
+        slot, _ = node_slots(bvh['bvh_left_child'], bvh['bvh_right_child'], bvh['bvh_prim_idx'] >= 0)
+        shell = shell_hint(new_sa, slot, int(info[1]), self._pack[0])
+        lay = build_mod.layout_of(old, tensors, info, perm, shell)
+        self._adopt_tree(lay, new_sa, s)
+        return maps, 'asked for'
 
     def remap_ids(self, ids, maps, out=None, stream=None):
         """An id image (trace_guides_ids) of this scene before a rebuild carried

@@ -162,15 +162,16 @@ class InteractiveViewer(MI355XRenderer):
         self.is_rendering_active = True
         print(f"\n{'─' * 60}\nCamera rotated - restarting render from sample 0\n{'─' * 60}")
 
-    def update_primitives(self, spheres=None, quads=None, triangles=None, rebuild=False, rebuild_growth=None):
-        """MI355XRenderer.update_primitives, ``rebuild`` and ``rebuild_growth``
-        included. What becomes of the temporal history is
-        ``_change_scene``'s rule."""
-        threshold = self._rebuild_threshold(rebuild, rebuild_growth)
+    def update_primitives(self, spheres=None, quads=None, triangles=None, rebuild=False, rebuild_growth=None,
+                          builder='host'):
+        """MI355XRenderer.update_primitives, ``rebuild``, ``rebuild_growth`` and
+        ``builder`` included. What becomes of the temporal
+        history is ``_change_scene``'s rule."""
+        threshold = self._rebuild_threshold(rebuild, rebuild_growth, builder)
 
         def change():
             self._apply_update(spheres, quads, triangles)
-            return self._rebuild_scene() if self._wants_rebuild(rebuild, threshold) else None
+            return self._rebuild_scene(builder) if self._wants_rebuild(rebuild, threshold) else None
         return self._change_scene(change, 'Scene updated')
 
     def update_materials(self, spheres=None, quads=None, triangles=None, media=None):
@@ -180,9 +181,10 @@ class InteractiveViewer(MI355XRenderer):
             self._apply_materials(spheres, quads, triangles, media)
         return self._change_scene(change, 'Materials updated')
 
-    def rebuild_bvh(self):
-        """MI355XRenderer.rebuild_bvh (DESIGN.md §20), the temporal history treated as by ``update_primitives``."""
-        return self._change_scene(self._rebuild_scene, 'BVH rebuilt')
+    def rebuild_bvh(self, builder='host'):
+        """MI355XRenderer.rebuild_bvh (DESIGN.md §20, §23), the temporal history treated as by ``update_primitives``."""
+        self._rebuild_threshold(False, None, builder)
+        return self._change_scene(lambda: self._rebuild_scene(builder), 'BVH rebuilt')
 
     def _change_scene(self, change, what):
         """Run ``change()``, which alters the scene and returns a rebuild's row

@@ -72,7 +72,7 @@ import time
 import numpy as np
 import torch
 
-from . import _lib, bvh as bvh_mod, core, device, scene_compiler, tree as tree_mod
+from . import _lib, build as build_mod, bvh as bvh_mod, core, device, scene_compiler, tree as tree_mod
 from .scene_data import STORAGE, SceneArrays
 
 # kernels.py:746: the reference's switch between its front-to-back stack
@@ -426,7 +426,7 @@ class MI355XRenderer:
     _REBUILD = 'for any other edit build a new MI355XRenderer from the edited world'
 
     def update_primitives(self, spheres=None, quads=None, triangles=None, keep_history=False, rebuild=False,
-                          rebuild_growth=None, **params):
+                          rebuild_growth=None, builder='host', **params):
         """Move primitives of the resident scene and refit its BVH on the device
         (DeviceScene.update_primitives, include/ptmi_update.h).
         Each argument maps a reference primitive index (the primitive's place
@@ -467,11 +467,13 @@ class MI355XRenderer:
         once more and does to the image what the update does: with
         ``keep_history`` the history's ids and primitive rows are carried to
         the new device order before the reprojection. Reference indices do
-        not change across a rebuild; the device rows in ``guides_ids()`` do."""
-        threshold = self._rebuild_threshold(rebuild, rebuild_growth)
+        not change across a rebuild; the device rows in ``guides_ids()`` do.
+        ``builder`` is ``rebuild_bvh``'s: with 'device' the default threshold
+        of 'auto' is ``ptmi.build.REBUILD_GROWTH_DEVICE``."""
+        threshold = self._rebuild_threshold(rebuild, rebuild_growth, builder)
         history = self._take_history(keep_history, params)
         self._apply_update(spheres, quads, triangles)
-        maps = self._rebuild_scene() if self._wants_rebuild(rebuild, threshold) else None
+        maps = self._rebuild_scene(builder) if self._wants_rebuild(rebuild, threshold) else None
         return self._after_scene_change(history, maps, params)
 
     def _take_history(self, keep_history, params):
@@ -504,9 +506,11 @@ class MI355XRenderer:
         return self.dscene.tree_growth()
 
     @staticmethod
-    def _rebuild_threshold(rebuild, rebuild_growth):
-        """update_primitives' ``rebuild`` and ``rebuild_growth`` checked: the growth
+    def _rebuild_threshold(rebuild, rebuild_growth, builder='host'):
+        """update_primitives' ``rebuild``, ``rebuild_growth`` and ``builder`` checked: the growth
         'auto' rebuilds above, else None."""
+        if builder not in ('host', 'device'):
+            raise ValueError(f"builder must be 'host' or 'device', not {builder!r}")
         if not (rebuild is True or rebuild is False or rebuild == 'auto'):
             raise ValueError(f"rebuild must be False, True or 'auto', not {rebuild!r}")
         if rebuild != 'auto':
@@ -514,10 +518,10 @@ class MI355XRenderer:
                 raise ValueError("rebuild_growth is the threshold of rebuild='auto'")
             return None
         if rebuild_growth is None:
-            rebuild_growth = tree_mod.REBUILD_GROWTH
+            rebuild_growth = build_mod.REBUILD_GROWTH_DEVICE if builder == 'device' else tree_mod.REBUILD_GROWTH
         if rebuild_growth is None:
             raise ValueError("rebuild='auto' needs rebuild_growth=: no default has been measured "
-                             "(ptmi.tree.REBUILD_GROWTH)")
+                             f"(ptmi.{'build.REBUILD_GROWTH_DEVICE' if builder == 'device' else 'tree.REBUILD_GROWTH'})")
         rebuild_growth = float(rebuild_growth)
         if not rebuild_growth >= 1.0:
             raise ValueError('rebuild_growth is a mean box-area growth: at least 1.0')
@@ -530,10 +534,10 @@ class MI355XRenderer:
             return self.last_tree_growth[0] > threshold
         return bool(rebuild)
 
-    def _rebuild_scene(self):
+    def _rebuild_scene(self, builder='host'):
         """DeviceScene.rebuild with no render in flight; bumps ``scene_revision``. Returns its row maps."""
         torch.cuda.synchronize(self.dscene.device)
-        maps = self.dscene.rebuild()
+        maps = self.dscene.rebuild(builder=builder)
         self.arrays = self.dscene.arrays
         self.scene_revision += 1
         self.bvh_rebuilds += 1
@@ -545,7 +549,7 @@ class MI355XRenderer:
         return _History(history.camera, history.guides, self.dscene.remap_ids(history.ids, maps),
                         self.dscene.permute_rows(history.rows, maps))
 
-    def rebuild_bvh(self, keep_history=False, **params):
+    def rebuild_bvh(self, keep_history=False, builder='host', **params):
         """Rebuild the resident scene's BVH in place (DeviceScene.rebuild,
         DESIGN.md §20): what a new renderer of the edited world would build,
         without a new renderer. The device tensors, their pointers, this
@@ -556,9 +560,13 @@ class MI355XRenderer:
         carried to the new device order first). The reference indices that
         ``update_primitives`` and ``primitives`` take do not change; the
         device rows in ``guides_ids()``'s id image do. Returns the fraction of
-        pixels with history (None without keep_history)."""
+        pixels with history (None without keep_history). ``builder='device'``
+        builds and packs the tree on the device (DeviceScene.rebuild, DESIGN.md
+        §23): the same tensors, maps and images byte for byte;
+        ``dscene.last_rebuild`` says which path ran."""
+        self._rebuild_threshold(False, None, builder)
         history = self._take_history(keep_history, params)
-        return self._after_scene_change(history, self._rebuild_scene(), params)
+        return self._after_scene_change(history, self._rebuild_scene(builder), params)
 
     # ------------------------------------------------------------ material edits
     _MATERIAL_KINDS = ('lambertian', 'metal', 'dielectric', 'diffuse_light')
