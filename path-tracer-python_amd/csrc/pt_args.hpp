@@ -1,6 +1,6 @@
 // pt_args.hpp — the argument checks every entry point of libptmi.so shares
 // (pt_abi.hip, pt_denoise.hip, pt_guide.hip, pt_reproject.hip, pt_motion.hip,
-// pt_update.hip, pt_tree.hip, pt_validate.hip, pt_material.hip).
+// pt_update.hip, pt_tree.hip, pt_validate.hip, pt_material.hip, pt_pose.hip).
 // Host only. The text of ptmi_last_error() and the render prologue are
 // pt_abi.hip's; the rest is inline.
 #pragma once

@@ -16,6 +16,10 @@
 //     faster on trees of a few thousand nodes, chosen by the caller.
 //   * upd_root: ref_nodes[0]'s box to the caller's float[6].
 //
+// The scene and topology checks and the launches of the refit and the root
+// copy are functions of their own (pt_update_launch.hpp): the pose ABI
+// (pt_pose.hip) runs the same step 2 after its own step 1.
+//
 // The arithmetic is pt_update_math.hpp's, shared with update_check.cpp. A few
 // thousand lanes of min / max: no LDS, no cross-lane reads, nothing timed by
 // ptmi_prof_*. No render kernel is involved.
@@ -23,6 +27,7 @@
 
 #include "../../include/ptmi_update.h"
 #include "pt_args.hpp"
+#include "pt_update_launch.hpp"
 #include "pt_update_math.hpp"
 
 namespace ptmi {
@@ -161,62 +166,46 @@ static bool upd_fill(UpdList& d, const ptmi_update_list* s, const float* prims, 
   return d.count >= 0 && d.count <= num_prims;
 }
 
-}  // namespace ptmi
-
-using namespace ptmi;
-
-extern "C" {
-
-int ptmi_update_primitives(const ptmi_scene_view* scene, const ptmi_update_list* spheres,
-                           const ptmi_update_list* quads, const ptmi_update_list* tris,
-                           const ptmi_update_topology* topo, float* root_box, void* stream) {
-  if (!scene) return fail(PTMI_EINVAL, "update: scene is NULL");
+// ---- the host half shared with the pose ABI (pt_update_launch.hpp)
+int upd_check_scene(const ptmi_scene_view* scene, const char* what) {
+  if (!scene) return fail(PTMI_EINVAL, "%s: scene is NULL", what);
   if (scene->n_inner < 0 || scene->num_bvh_nodes < 0 || scene->num_spheres < 0 || scene->num_quads < 0 ||
       scene->num_triangles < 0 || (scene->n_inner > 0 && scene->num_bvh_nodes != 2 * scene->n_inner + 1))
-    return fail(PTMI_EINVAL, "update: bad scene counts (num_bvh_nodes must be 2 * n_inner + 1)");
-  UpdList s, q, t;
-  if (!upd_fill(s, spheres, scene->spheres, scene->num_spheres, 0, 4, 4))
-    return fail(PTMI_EINVAL, "update: sphere count negative or above num_spheres");
-  if (!upd_fill(q, quads, scene->quads, scene->num_quads, 2, 16, 9))
-    return fail(PTMI_EINVAL, "update: quad count negative or above num_quads");
-  if (!upd_fill(t, tris, scene->tris, scene->num_triangles, 1, 12, 9))
-    return fail(PTMI_EINVAL, "update: triangle count negative or above num_triangles");
-  const struct {
-    const UpdList& l;
-    const char* name;
-  } lists[3] = {{s, "sphere"}, {q, "quad"}, {t, "triangle"}};
-  for (const auto& e : lists)
-    if (e.l.count > 0 && (bad4(e.l.prim) || bad4(e.l.leaf) || bad4(e.l.row) || bad4(e.l.build) || bad4(e.l.prims)))
-      return fail(PTMI_EINVAL, "update: a %s list pointer is NULL/misaligned", e.name);
+    return fail(PTMI_EINVAL, "%s: bad scene counts (num_bvh_nodes must be 2 * n_inner + 1)", what);
+  return PTMI_OK;
+}
+
+int upd_check_tree(const ptmi_scene_view* scene, const ptmi_update_topology* topo, const float* root_box,
+                   int64_t n_edits, const char* what) {
   const int32_t n_inner = scene->n_inner;
-  const int64_t n_edits = (int64_t)s.count + q.count + t.count;
   if ((n_inner > 0 || n_edits > 0) && bad4(scene->ref_nodes))
-    return fail(PTMI_EINVAL, "update: ref_nodes NULL/misaligned");
+    return fail(PTMI_EINVAL, "%s: ref_nodes NULL/misaligned", what);
   if (n_inner > 0) {
-    if (bad16(scene->nodes)) return fail(PTMI_EINVAL, "update: nodes NULL/misaligned");
-    if (!topo) return fail(PTMI_EINVAL, "update: topo is NULL");
-    if (bad4(topo->order)) return fail(PTMI_EINVAL, "update: order NULL/misaligned");
-    if (bad4(topo->slot)) return fail(PTMI_EINVAL, "update: slot NULL/misaligned");
-    if (bad4(root_box)) return fail(PTMI_EINVAL, "update: root_box NULL/misaligned");
+    if (bad16(scene->nodes)) return fail(PTMI_EINVAL, "%s: nodes NULL/misaligned", what);
+    if (!topo) return fail(PTMI_EINVAL, "%s: topo is NULL", what);
+    if (bad4(topo->order)) return fail(PTMI_EINVAL, "%s: order NULL/misaligned", what);
+    if (bad4(topo->slot)) return fail(PTMI_EINVAL, "%s: slot NULL/misaligned", what);
+    if (bad4(root_box)) return fail(PTMI_EINVAL, "%s: root_box NULL/misaligned", what);
     if (!topo->level_end || topo->n_levels < 1)
-      return fail(PTMI_EINVAL, "update: level_end is NULL or n_levels < 1");
+      return fail(PTMI_EINVAL, "%s: level_end is NULL or n_levels < 1", what);
     int32_t prev = 0;
     for (int32_t j = 0; j < topo->n_levels; ++j) {
       if (topo->level_end[j] <= prev || topo->level_end[j] > n_inner)
-        return fail(PTMI_EINVAL, "update: level ends must ascend strictly to n_inner");
+        return fail(PTMI_EINVAL, "%s: level ends must ascend strictly to n_inner", what);
       prev = topo->level_end[j];
     }
-    if (prev != n_inner) return fail(PTMI_EINVAL, "update: level ends must ascend strictly to n_inner");
-    if (topo->flags & ~PTMI_UPDATE_ONE_GROUP) return fail(PTMI_EINVAL, "update: unknown flags");
+    if (prev != n_inner) return fail(PTMI_EINVAL, "%s: level ends must ascend strictly to n_inner", what);
+    if (topo->flags & ~PTMI_UPDATE_ONE_GROUP) return fail(PTMI_EINVAL, "%s: unknown flags", what);
     if ((topo->flags & PTMI_UPDATE_ONE_GROUP) && topo->n_levels > PTMI_UPDATE_ONE_GROUP_MAX_LEVELS)
-      return fail(PTMI_EINVAL, "update: too many levels for PTMI_UPDATE_ONE_GROUP");
+      return fail(PTMI_EINVAL, "%s: too many levels for PTMI_UPDATE_ONE_GROUP", what);
   }
-  if (scene->num_bvh_nodes == 0) return PTMI_OK;
+  return PTMI_OK;
+}
+
+void upd_refit_launch(const ptmi_scene_view* scene, const ptmi_update_topology* topo, float* root_box, void* stream) {
   hipStream_t st = (hipStream_t)stream;
+  const int32_t n_inner = scene->n_inner;
   float* ref_nodes = const_cast<float*>(scene->ref_nodes);
-  if (n_edits > 0)
-    hipLaunchKernelGGL(upd_leaves, dim3((unsigned)((n_edits + kUpdBlock - 1) / kUpdBlock)), dim3(kUpdBlock), 0, st, s, q,
-                       t, ref_nodes, scene->num_bvh_nodes);
   if (n_inner > 0 && (topo->flags & PTMI_UPDATE_ONE_GROUP)) {
     UpdLevels lv;
     lv.n = topo->n_levels;
@@ -234,6 +223,39 @@ int ptmi_update_primitives(const ptmi_scene_view* scene, const ptmi_update_list*
     }
   }
   if (root_box && ref_nodes) hipLaunchKernelGGL(upd_root, dim3(1), dim3(64), 0, st, ref_nodes, root_box);
+}
+
+}  // namespace ptmi
+
+using namespace ptmi;
+
+extern "C" {
+
+int ptmi_update_primitives(const ptmi_scene_view* scene, const ptmi_update_list* spheres,
+                           const ptmi_update_list* quads, const ptmi_update_list* tris,
+                           const ptmi_update_topology* topo, float* root_box, void* stream) {
+  if (int rc = upd_check_scene(scene, "update")) return rc;
+  UpdList s, q, t;
+  if (!upd_fill(s, spheres, scene->spheres, scene->num_spheres, 0, 4, 4))
+    return fail(PTMI_EINVAL, "update: sphere count negative or above num_spheres");
+  if (!upd_fill(q, quads, scene->quads, scene->num_quads, 2, 16, 9))
+    return fail(PTMI_EINVAL, "update: quad count negative or above num_quads");
+  if (!upd_fill(t, tris, scene->tris, scene->num_triangles, 1, 12, 9))
+    return fail(PTMI_EINVAL, "update: triangle count negative or above num_triangles");
+  const struct {
+    const UpdList& l;
+    const char* name;
+  } lists[3] = {{s, "sphere"}, {q, "quad"}, {t, "triangle"}};
+  for (const auto& e : lists)
+    if (e.l.count > 0 && (bad4(e.l.prim) || bad4(e.l.leaf) || bad4(e.l.row) || bad4(e.l.build) || bad4(e.l.prims)))
+      return fail(PTMI_EINVAL, "update: a %s list pointer is NULL/misaligned", e.name);
+  const int64_t n_edits = (int64_t)s.count + q.count + t.count;
+  if (int rc = upd_check_tree(scene, topo, root_box, n_edits, "update")) return rc;
+  if (scene->num_bvh_nodes == 0) return PTMI_OK;
+  if (n_edits > 0)
+    hipLaunchKernelGGL(upd_leaves, dim3((unsigned)((n_edits + kUpdBlock - 1) / kUpdBlock)), dim3(kUpdBlock), 0,
+                       (hipStream_t)stream, s, q, t, const_cast<float*>(scene->ref_nodes), scene->num_bvh_nodes);
+  upd_refit_launch(scene, topo, root_box, stream);
   return hip_result(hipGetLastError());
 }
 

@@ -386,6 +386,22 @@ class triangle(hittable):
         self.bbox = aabb.from_points(lo, hi)
         self.bbox._pad_to_minimums()
 
+    @classmethod
+    def translated(cls, tri, offset):
+        """``tri`` moved by ``offset``: the vertices each + offset, the edges and
+        the normal kept from ``tri`` (a translation does not change them; formed
+        anew from the moved float64 vertices their last bits would), the box
+        from the new vertices (ptmi.pose)."""
+        t = cls.__new__(cls)
+        t.v0, t.v1, t.v2, t.mat = tri.v0 + offset, tri.v1 + offset, tri.v2 + offset, tri.mat
+        t.edge1, t.edge2, t.normal = tri.edge1, tri.edge2, tri.normal
+        v0, v1, v2 = t.v0, t.v1, t.v2
+        lo = point3(min(v0.x, v1.x, v2.x), min(v0.y, v1.y, v2.y), min(v0.z, v1.z, v2.z))
+        hi = point3(max(v0.x, v1.x, v2.x), max(v0.y, v1.y, v2.y), max(v0.z, v1.z, v2.z))
+        t.bbox = aabb.from_points(lo, hi)
+        t.bbox._pad_to_minimums()
+        return t
+
 
 class hittable_list(hittable):
     def __init__(self):

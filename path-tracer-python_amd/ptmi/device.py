@@ -15,9 +15,10 @@ import os
 import numpy as np
 import torch
 
-from . import _lib, build as build_mod, bvh as bvh_mod, guide, material, motion, post, temporal, tree, update, validate, wf_tiles
-from .scene_data import (BVH_KEYS, ByCode, ByStorage, DeviceLayout, KINDS, STORAGE, SceneArrays, camera_upload,
-                         counts_by_code, node_slots, pack_device, shell_hint)
+from . import (_lib, build as build_mod, bvh as bvh_mod, guide, material, motion, pose as pose_mod, post, temporal,
+               tree, update, validate, wf_tiles)
+from .scene_data import (BVH_KEYS, ByCode, ByStorage, DeviceLayout, KINDS, PRIM_SPHERE, STORAGE, SceneArrays,
+                         camera_upload, counts_by_code, find_shell, node_slots, pack_device, shell_hint)
 
 
 def _stream_or_current(stream, device=None):
@@ -56,6 +57,8 @@ class DeviceScene:
         self._pack = (node_bytes, leaf_order)  # rebuild packs as the scene was packed
         self._builder = None  # rebuild(builder='device')'s device buffers, made by its first call
         self.last_rebuild = None  # {'builder': 'host' | 'device', 'reason': ...} of the last rebuild
+        self._tracks = None  # set_tracks' resident tracks, rest edit list, shutter range and posed shell hint
+        self.posed = None  # the time pose() last put the tracked primitives at; None: the rest scene
         dev = torch.device(device if device is not None else 'cuda')
         if dev.type != 'cuda':
             raise _lib.PtmiError(f'DeviceScene needs a cuda device, got {dev}')
@@ -115,6 +118,7 @@ class DeviceScene:
         a ByStorage ``(spheres, quads, tris)``: the "previous rows" of a
         motion-aware reprojection (Integrator.reproject_moved), taken before an
         update. Asynchronous on ``stream``."""
+        self._require_unposed()
         with torch.cuda.device(self.device), torch.cuda.stream(_stream_or_current(stream, self.device)):
             return ByStorage(*(getattr(self, k.tensor).clone() for k in STORAGE))
 
@@ -185,9 +189,14 @@ class DeviceScene:
         (scene_data.find_shell on the mirror; 0 if the claim no longer holds).
         Topology, materials and counts do not change: materials are
         update_materials', for anything else build a new DeviceScene. ``flags``
-        as for update_call (same bits either way)."""
+        as for update_call (same bits either way). Tracks (set_tracks) are
+        dropped if an edit names a tracked primitive: their rest rows are stale."""
+        self._require_unposed()
         st = self._update_state()
         edits = update.check_edits(counts_by_code(self.layout), spheres, quads, triangles)
+        if self._tracks is not None and any(np.intersect1d(idx, self._tracks['indices'].get(t, ())).size
+                                            for t, (idx, _, _) in edits.items()):
+            self._tracks = None
         self._upload_edits(st, edits, stream, flags)
         _stream_or_current(stream, self.device).synchronize()
         update.refresh_mirror(self.arrays, self.layout, st, edits,
@@ -196,6 +205,10 @@ class DeviceScene:
 
     def _upload_edits(self, st, edits, stream, flags):
         """The checked edits to the device in one int and one float tensor, and update_call on them."""
+        self.update_call(self._edit_lists(st, edits)[0], stream, flags)
+
+    def _edit_lists(self, st, edits):
+        """The checked edits on the device in one int and one float tensor: (update_call's lists, the tensors)."""
         ints, floats, lists, ni, nf = [], [], {}, 0, 0
         for t, (idx, rows, build) in edits.items():
             n = idx.size
@@ -208,7 +221,134 @@ class DeviceScene:
             tf = torch.from_numpy(np.concatenate(floats)).to(self.device)
             pi, pf = ti.data_ptr(), tf.data_ptr()
             lists = {t: (pi + 4 * a, pi + 4 * b, pf + 4 * c, pf + 4 * d, n) for t, (a, b, c, d, n) in lists.items()}
-        self.update_call(lists, stream, flags)
+            return lists, (ti, tf)
+        return lists, ()
+
+    # ------------------------------------------------ poses of moving primitives (ptmi.pose)
+    def _require_unposed(self):
+        if self.posed is not None:
+            raise _lib.PtmiError(f'the scene is posed at t = {self.posed!r}: unpose() first')
+
+    def set_tracks(self, spheres=None, quads=None, triangles=None, t_range=(0.0, 1.0)):
+        """Make the tracks of moving primitives resident (include/ptmi_pose.h,
+        DESIGN.md §24). Each argument is ``(reference primitive indices, (n, 6 /
+        9 / 12) f64 records)``: sphere {o, d}, quad {Q, d, normal}, triangle
+        {v0, v1, v2, d} (``pose.track_records``); indices out of range or
+        repeated and records of another shape or not finite are a ValueError.
+        With them a *rest* edit list is uploaded: the mirror's own rows and
+        build records of the tracked primitives, which ``unpose`` writes back.
+        ``t_range``: the times ``pose`` will take. The shell hint of the posed
+        scene is evaluated here, once: the scene is posed at both ends of the
+        range, every tracked leaf gets the union of its two boxes (the box at
+        any time between lies inside it: every step of the arithmetic is
+        monotone in t), and the layout's hint is kept if ``find_shell`` on
+        those boxes names the same leaf and that sphere is not tracked; else
+        the posed hint is 0. The scene is left unposed. Replaces earlier
+        tracks; no arguments clears them."""
+        self._require_unposed()
+        st = self._update_state()
+        (t0, t1), _ = pose_mod.check_shutter(t_range, 1)
+        tracks = pose_mod.check_tracks(counts_by_code(self.layout), spheres, quads, triangles)
+        ints, recs, lists, ni, nr = [], [], {}, 0, 0
+        for t, (idx, rec) in tracks.items():
+            n = idx.size
+            ints += [st['dev_of'][t][idx].astype(np.int32), st['leaf_of'][t][idx].astype(np.int32)]
+            recs.append(rec.reshape(-1))
+            lists[t] = (ni, ni + n, nr, n)  # element offsets, made pointers below
+            ni, nr = ni + 2 * n, nr + rec.size
+        keep = ()
+        if ints:
+            ti = torch.from_numpy(np.concatenate(ints)).to(self.device)
+            tr = torch.from_numpy(np.concatenate(recs)).to(self.device)  # f64: torch allocations are 8-B aligned
+            pi, pr = ti.data_ptr(), tr.data_ptr()
+            lists = {t: (pi + 4 * a, pi + 4 * b, pr + 8 * c, n) for t, (a, b, c, n) in lists.items()}
+            keep = (ti, tr)
+        indices = {t: idx for t, (idx, _) in tracks.items()}
+        rest, rest_keep = self._edit_lists(st, update.current_edits(self.arrays, self.layout, st, indices))
+        self._tracks = {'lists': lists, 'rest': rest, 'keep': keep + rest_keep, 'indices': indices,
+                        't_range': (t0, t1), 'shell': 0}
+        self._tracks['shell'] = self._posed_shell(st, indices, t0, t1)
+
+    def _posed_shell(self, st, indices, t0, t1):
+        """The shell hint valid at every pose in [t0, t1] (set_tracks): the layout's, or 0."""
+        lay, sa = self.layout, self.arrays
+        if not lay.shell or not indices:
+            return int(lay.shell)
+        s = torch.cuda.current_stream(self.device)
+        boxes = []
+        try:
+            for t in (t0, t1):
+                self.pose(t, s)
+                boxes.append(self.t_ref_nodes.cpu().numpy().reshape(-1, 12)[:sa.num_bvh_nodes].copy())
+        finally:
+            self.unpose(s)
+        bmin, bmax = sa.bvh['bvh_bbox_min'].copy(), sa.bvh['bvh_bbox_max'].copy()
+        for t, idx in indices.items():
+            leaves = st['leaf_of'][t][idx]
+            bmin[leaves] = np.minimum(boxes[0][leaves, 0:3], boxes[1][leaves, 0:3])
+            bmax[leaves] = np.maximum(boxes[0][leaves, 4:7], boxes[1][leaves, 4:7])
+        swept = dataclasses.replace(sa, bvh=dict(sa.bvh, bvh_bbox_min=bmin, bvh_bbox_max=bmax))
+        leaf = find_shell(swept, lay.max_leaf_depth)
+        if leaf <= 0 or shell_hint(swept, st['slot_np'], lay.max_leaf_depth, self._pack[0]) != lay.shell:
+            return 0
+        tracked = indices.get(PRIM_SPHERE)
+        if tracked is not None and int(sa.bvh['bvh_prim_idx'][leaf]) in set(tracked.tolist()):
+            return 0
+        return int(lay.shell)
+
+    def pose_call(self, t, stream=None, flags=None):
+        """ptmi_pose_primitives on this scene's resident tracks at time ``t``:
+        asynchronous; the view's host fields and ``posed`` are not touched
+        (``pose`` does both). ``flags`` as for update_call."""
+        tr = self._tracks
+        if tr is None:
+            raise _lib.PtmiError('pose needs set_tracks() first')
+        t = float(t)
+        if not tr['t_range'][0] <= t <= tr['t_range'][1]:
+            raise ValueError(f'pose: t = {t!r} is outside the tracks\' t_range {tr["t_range"]}')
+        st = self._update_state()
+        if flags is None:
+            flags = update.refit_flags(self.layout.n_inner, st['n_levels'])
+        arg = [C.byref(pose_mod.PoseList(*e)) if e is not None and e[3] else None
+               for e in (tr['lists'].get(k.code) for k in STORAGE)]
+        topo = update.UpdateTopology(st['order'].data_ptr() if st['order'] is not None else None,
+                                     st['slot'].data_ptr() if st['slot'] is not None else None,
+                                     st['level_end'], st['n_levels'], int(flags))
+        with torch.cuda.device(self.device):
+            _lib.check(pose_mod.load().ptmi_pose_primitives(self.view, arg[0], arg[1], arg[2], t, C.byref(topo),
+                                                            st['root'].data_ptr(), _stream_ptr(stream, self.device)),
+                       'ptmi_pose_primitives')
+        return t
+
+    def pose(self, t, stream=None, flags=None):
+        """Put the tracked primitives where they are at time ``t`` and refit
+        (ptmi_pose_primitives): afterwards the device holds byte for byte what
+        ``update_primitives(*pose.posed_records(tracks, t))`` leaves. ``t``
+        outside set_tracks' ``t_range`` is a ValueError. One 24-byte readback
+        of the root box refreshes the view; the view's shell hint becomes the
+        posed one, and ``posed`` is ``t``. The mirror (``arrays``) and
+        ``layout`` keep describing the rest scene; ``unpose`` brings it back
+        (``pose(0.0)`` does not: Q + 0.0 * d turns a -0.0 into +0.0). No
+        render of this scene may be in flight on another stream. ``flags`` as
+        for update_call."""
+        s = _stream_or_current(stream, self.device)
+        self.posed = self.pose_call(t, s, flags)
+        if self.view.num_bvh_nodes:
+            with torch.cuda.device(self.device), torch.cuda.stream(s):
+                root = self._upd['root'].cpu().numpy()  # waits for the call on its stream
+            self.view.root_min[:], self.view.root_max[:] = [float(x) for x in root[:3]], [float(x) for x in root[3:]]
+        self.view.shell = int(self._tracks['shell'])
+
+    def unpose(self, stream=None):
+        """The rest scene back on the device: ptmi_update_primitives on the
+        resident rest list restores every byte a pose changed; the view's root
+        box and shell hint are the layout's again and ``posed`` is None.
+        Asynchronous on ``stream``; nothing to do for an unposed scene."""
+        if self.posed is None:
+            return
+        self.update_call(self._tracks['rest'], stream)
+        self.posed = None
+        self._set_tree(self.layout)
 
     # ------------------------------------------------ material edits (ptmi.material)
     def material_call(self, lists, stream=None):
@@ -243,6 +383,7 @@ class DeviceScene:
         a shell sphere that stops being a medium clears it, an enclosing
         sphere that becomes one may gain it. Geometry, counts, topology, texels
         and the growth baseline do not change."""
+        self._require_unposed()
         st = self._update_state()
         edits = material.check_edits(counts_by_code(self.layout), len(self.layout.img_w), spheres, quads, triangles)
         s = _stream_or_current(stream, self.device)
@@ -290,6 +431,7 @@ class DeviceScene:
         or freshly rebuilt tree, growing as update_primitives scatters the
         primitives of a refit tree. One launch on ``stream`` and one 16-byte
         readback."""
+        self._require_unposed()
         st = self._tree_state()
         s = _stream_or_current(stream, self.device)
         with torch.cuda.device(self.device), torch.cuda.stream(s):
@@ -331,6 +473,7 @@ class DeviceScene:
         which path ran and why."""
         if builder not in ('host', 'device'):
             raise ValueError(f"builder must be 'host' or 'device', not {builder!r}")
+        self._require_unposed()
         self._update_state()  # the mirror (and the check that the scene was made from SceneArrays)
         s = _stream_or_current(stream, self.device)
         reason = 'asked for'
@@ -364,6 +507,7 @@ class DeviceScene:
     def _adopt_tree(self, lay, new_sa, s):
         """After a rebuild on either path: the new layout and mirror, the view, the update topology, the baseline."""
         self.layout, self.arrays = lay, new_sa
+        self._tracks = None  # device rows, leaves and rest rows are those of the old tree
         self._set_tree(lay)
         self._upd = self._topology_state()  # leaf_of and dev_of of the new tree; the mirror is this scene's own already
         self._take_baseline(s)
@@ -974,6 +1118,37 @@ class Integrator:
                                                  weight.data_ptr() if weight is not None else None,
                                                  self._stream(stream)), 'ptmi_history_validate')
         return out_accum, out_stats
+
+    # ------------------------------------------------ motion blur by poses (ptmi.pose)
+    def render_posed(self, render_fn, frame, sample_begin, sample_count, slice_spp, shutter, *args, stream=None,
+                     **kwargs):
+        """Samples [sample_begin, sample_begin + sample_count) rendered as a
+        sequence of poses of the scene's tracks (DeviceScene.set_tracks,
+        DESIGN.md §24): the range is split on the global slice boundaries
+        (``pose.slice_times``: sample s belongs to slice s // slice_spp, however
+        the render is chunked), and for every slice the scene is posed at the
+        slice's shutter time and ``render_fn(frame, *args, begin, count,
+        **kwargs)`` renders the overlap: ``render_mk`` with ``args = (accum,)``,
+        ``render_mk_stats`` with ``(accum, stats)`` and ``tiles=``. A pose
+        writes the scene, so its stream first waits for every overlapped trace
+        in flight: overlapped megakernel calls never straddle a pose, within a
+        slice they stay overlapped; the pose's own root readback has finished
+        it before the slice's first trace is launched on any stream. The scene
+        is left posed: the caller unposes (``unpose``)."""
+        dev = self.scene.device
+        s = _stream_or_current(stream, dev)
+        if stream is not None:
+            kwargs['stream'] = stream
+        for _, t, begin, n in pose_mod.slice_times(sample_begin, sample_count, slice_spp, shutter):
+            self._after_traces(s)
+            self.scene.pose(t, s)
+            render_fn(frame, *args, begin, n, **kwargs)
+
+    def unpose(self, stream=None):
+        """The scene's rest state back (DeviceScene.unpose), after every overlapped trace in flight."""
+        s = _stream_or_current(stream, self.scene.device)
+        self._after_traces(s)
+        self.scene.unpose(s)
 
     def _after_traces(self, stream):
         """Make `stream` wait for the overlapped traces in flight: they add to

@@ -254,7 +254,11 @@ class InteractiveViewer(MI355XRenderer):
         with or without ``target_error``, the guides of the camera are traced
         once, and a call that follows a reprojecting restart keeps the
         history: sample index ``next_sample_index`` goes on where the last
-        render stopped, and the image divides each pixel by its own count."""
+        render stopped, and the image divides each pixel by its own count.
+
+        With the renderer's ``shutter`` (a keyword of the constructor, like
+        ``slice_spp``) every step goes through the same pose sequence as the
+        renderer's own calls (MI355XRenderer._trace)."""
         spp = int(self.cam.samples_per_pixel)
         print('\nInteractiveViewer')
         print(f'Resolution: {self.cam.img_width}x{self.cam.img_height} | Max Samples: {spp} | Depth: {self.max_depth}')
@@ -299,9 +303,10 @@ class InteractiveViewer(MI355XRenderer):
                 n = 1  # the reference prints sample 1
             t = time.time()
             if not stats_path:
-                self.integrator.render_mk(self.frame, self.accum, self.current_sample, n)
+                self._trace(self.integrator.render_mk, self.accum, begin=self.current_sample, count=n)
             else:
-                self.integrator.render_mk_stats(self.frame, self.accum, self.stats, self.next_sample_index, n)
+                self._trace(self.integrator.render_mk_stats, self.accum, self.stats, begin=self.next_sample_index,
+                            count=n)
                 if target_error is not None:
                     left = self.integrator.tile_update(self.frame, self.stats, target_error, min_spp, spp,
                                                        self._tiles)

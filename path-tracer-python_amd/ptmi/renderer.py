@@ -61,6 +61,14 @@ where a window of pixels says the light has changed (a moved shadow, a
 reflection) and merges the rest (DESIGN.md §21);
 InteractiveViewer(temporal=True, validate=True) does so after every
 reprojecting restart. Derived state: not checkpointed.
+
+Motion blur (the reference's Taichi kernels render ``Sphere.moving`` frozen at
+t = 0, quirk Q22; its CPU renderers blur): with ``shutter=(t0, t1)`` every
+render call traces each slice of ``slice_spp`` samples with the moving
+primitives posed at that slice's shutter time (ptmi.pose) and
+leaves the device at the rest scene. Moving spheres are tracked by themselves;
+``set_motion`` gives quads and triangles a displacement. ``shutter=None``, the
+default, renders as before and makes no pose call.
 """
 from __future__ import annotations
 
@@ -72,7 +80,7 @@ import time
 import numpy as np
 import torch
 
-from . import _lib, build as build_mod, bvh as bvh_mod, core, device, scene_compiler, tree as tree_mod
+from . import _lib, build as build_mod, bvh as bvh_mod, core, device, pose as pose_mod, scene_compiler, tree as tree_mod
 from .scene_data import STORAGE, SceneArrays
 
 # kernels.py:746: the reference's switch between its front-to-back stack
@@ -95,7 +103,8 @@ class _History:
 
 
 class MI355XRenderer:
-    def __init__(self, world, cam, img_path: str, seed: int = 0, samples_per_launch: int = 0, device_id=None):
+    def __init__(self, world, cam, img_path: str, seed: int = 0, samples_per_launch: int = 0, device_id=None,
+                 shutter=None, slice_spp=pose_mod.SLICE_SPP):
         self.timing = {'taichi_init': 0.0, 'scene_compile': 0.0, 'bvh_compile': 0.0, 'bvh_flatten': 0.0,
                        'camera_upload': 0.0, 'gpu_upload': 0.0, 'kernel_warmup': 0.0, 'total_setup': 0.0}
         self.sample_times = []
@@ -141,6 +150,13 @@ class MI355XRenderer:
         # rebuild_bvh() and update_primitives(rebuild=...): rebuilds done, and the (mean, max) growth 'auto' last read
         self.bvh_rebuilds = 0
         self.last_tree_growth = None
+        # motion blur (ptmi.pose): the shutter interval (None: off), the samples per pose, set_motion's displacements
+        # of quads and triangles, and (scene_revision, motion edits, shutter) the resident tracks were made for
+        self.shutter = shutter
+        self.slice_spp = slice_spp
+        self._motion = {'quads': {}, 'triangles': {}}
+        self._motion_edits = 0
+        self._tracks_key = None
         # launches per progress report: one launch renders many samples (path regeneration)
         self.samples_per_launch = int(samples_per_launch)
         device.require_gpu()
@@ -196,7 +212,60 @@ class MI355XRenderer:
         """One sample of every pixel (renderer.py:551-556): sample index
         ``sample`` of the counter-based stream, megakernel."""
         self._integrator_label = 'megakernel'
-        self.integrator.render_mk(self.frame, self.accum, int(sample), 1)
+        self._trace(self.integrator.render_mk, self.accum, begin=int(sample), count=1)
+
+    # ------------------------------------------------------------ motion blur
+    def set_motion(self, spheres=None, quads=None, triangles=None):
+        """Give primitives a linear motion for ``shutter`` renders (DESIGN.md
+        §24). Each argument maps a reference primitive index (as in
+        ``primitives``) to a ``vec3`` displacement over unit time; None as a
+        value removes the motion. For a sphere the displacement replaces its
+        ``center.direction`` (``primitives`` then holds a copy of the object);
+        quads and triangles keep theirs in the renderer. The resident scene,
+        which is the rest pose, does not change, and neither does the image."""
+        given = {'spheres': spheres or {}, 'quads': quads or {}, 'triangles': triangles or {}}
+        for name, new in given.items():
+            have = self._prims[name]
+            for i, d in new.items():
+                if not isinstance(i, (int, np.integer)) or not 0 <= i < len(have):
+                    raise ValueError(f'{name}: no primitive {i!r} (the scene has {len(have)})')
+                if d is not None and not (isinstance(d, core.vec3) and all(np.isfinite(d.to_list()))):
+                    raise ValueError(f'{name}[{i}]: the displacement must be a finite vec3 or None')
+        for i, d in given['spheres'].items():
+            obj = copy.copy(self._prims['spheres'][i])
+            obj.center = core._center(obj.center.origin, d.copy() if d is not None else core.vec3(0, 0, 0))
+            self._prims['spheres'][i] = obj
+        for name in ('quads', 'triangles'):
+            for i, d in given[name].items():
+                if d is None:
+                    self._motion[name].pop(int(i), None)
+                else:
+                    self._motion[name][int(i)] = d.copy()
+        self._motion_edits += 1
+
+    def _ensure_tracks(self):
+        """The resident tracks of the scene as it is now: made on the first use, remade when the scene, the
+        motion or the shutter has changed since (or the scene dropped them)."""
+        shutter, self.slice_spp = pose_mod.check_shutter(self.shutter, self.slice_spp)
+        key = (self.scene_revision, self._motion_edits, shutter)
+        if key != self._tracks_key or self.dscene._tracks is None:
+            torch.cuda.synchronize(self.dscene.device)  # set_tracks poses the scene: no render in flight
+            tracks = pose_mod.tracks_of(self._prims, self._motion)
+            self.dscene.set_tracks(*pose_mod.track_records(tracks), t_range=shutter)
+            self._tracks_key = key
+        return shutter
+
+    def _trace(self, render_fn, *buffers, begin, count, **kwargs):
+        """``render_fn(frame, *buffers, begin, count, **kwargs)``, or with a shutter the same samples through
+        Integrator.render_posed, slice by slice, and the device back at the rest scene whatever happens."""
+        if self.shutter is None:
+            return render_fn(self.frame, *buffers, begin, count, **kwargs)
+        shutter = self._ensure_tracks()
+        try:
+            self.integrator.render_posed(render_fn, self.frame, begin, count, self.slice_spp, shutter, *buffers,
+                                         **kwargs)
+        finally:
+            self.integrator.unpose()
 
     def _drop_denoised(self):
         self.denoised = self.denoised_var = self.denoise_seconds = None
@@ -246,7 +315,7 @@ class MI355XRenderer:
         while done < spp:
             n = min(per, spp - done)
             t = time.time()
-            render_fn(self.frame, self.accum, done, n)
+            self._trace(render_fn, self.accum, begin=done, count=n)
             torch.cuda.synchronize(self.dscene.device)
             dt = time.time() - t
             self.sample_times += [dt / n] * n
@@ -333,8 +402,8 @@ class MI355XRenderer:
             active = tiles['n']
             t = time.time()
             sel = (tiles['list'], active) if listed and active < ntiles else None
-            (integ.render_mk_stats if mk else integ.render_wf_stats)(self.frame, self.accum, self.stats,
-                                                                     self.current_sample, n, sel)
+            self._trace(integ.render_mk_stats if mk else integ.render_wf_stats, self.accum, self.stats,
+                        begin=self.current_sample, count=n, tiles=sel)
             integ.tile_update(self.frame, self.stats, target_error, min_spp, max_spp, tiles)
             torch.cuda.synchronize(self.dscene.device)
             dt = time.time() - t
@@ -798,8 +867,8 @@ class MI355XRenderer:
         self._integrator_label = 'adaptive-' + integrator
         begin = getattr(self, 'next_sample_index', self.current_sample)
         t = time.time()
-        (integ.render_mk_stats if integrator == 'megakernel' else integ.render_wf_stats)(
-            self.frame, fresh_accum, fresh_stats, begin, spp)
+        self._trace(integ.render_mk_stats if integrator == 'megakernel' else integ.render_wf_stats,
+                    fresh_accum, fresh_stats, begin=begin, count=spp)
         hist = (self.accum, self.stats)
         out = integ.validate_history(*hist, fresh_accum, fresh_stats, out=sc['out'], weight=sc['weight'], **params)
         # sum(n_v) / sum(n_h): n_v = weight * n_h, whole numbers; a non-finite history pixel counts as empty
@@ -855,6 +924,9 @@ class MI355XRenderer:
     # a render resumed with the other one would match neither uninterrupted render
     _STATE_KEYS = ('integrator', 'seed', 'max_depth', 'background', 'traversal', 'width', 'height', 'camera',
                    'scene')
+    # the shutter and the samples per pose: absent from a checkpoint written before there was a shutter, which is
+    # one of an unblurred render
+    _SHUTTER_KEYS = {'shutter': np.zeros(0, np.float64), 'slice_spp': np.int64(0)}
 
     def _render_state(self):
         import hashlib
@@ -868,7 +940,13 @@ class MI355XRenderer:
         return {'integrator': np.array(self._integrator_label), 'seed': np.int64(f.seed), 'max_depth': np.int64(f.max_depth),
                 'background': np.array(list(f.bg), np.float32), 'traversal': np.int64(f.traversal),
                 'width': np.int64(f.width), 'height': np.int64(f.height), 'camera': cam,
-                'scene': np.array(h.hexdigest())}
+                'scene': np.array(h.hexdigest()), **self._shutter_state()}
+
+    def _shutter_state(self):
+        if self.shutter is None:
+            return dict(self._SHUTTER_KEYS)
+        shutter, slice_spp = pose_mod.check_shutter(self.shutter, self.slice_spp)
+        return {'shutter': np.array(shutter, np.float64), 'slice_spp': np.int64(slice_spp)}
 
     def save_checkpoint(self, path):
         """Write the accumulator and the next sample index (plain arrays, npz)
@@ -910,6 +988,7 @@ class MI355XRenderer:
             if missing:
                 raise ValueError(f'{path} is not a checkpoint of this renderer version (missing {missing})')
             state = {k: z[k].copy() for k in self._STATE_KEYS}
+            state.update({k: z[k].copy() if k in z.files else v for k, v in self._SHUTTER_KEYS.items()})
             acc = z['accum'].copy()
             nxt = int(z['next_sample'])
             ad = {k: z[k].copy() for k in ('stats', 'tile_state', 'tile_err', 'adaptive', 'adaptive_passes',
@@ -940,7 +1019,7 @@ class MI355XRenderer:
 
     def _check_resume_state(self):
         cur = self._render_state()
-        for k in self._STATE_KEYS:
+        for k in self._STATE_KEYS + tuple(self._SHUTTER_KEYS):
             if not np.array_equal(cur[k], self._resume_state[k]):
                 raise ValueError(f'checkpoint was written for another render: {k} differs')
         if tuple(self.accum.shape) != (int(cur['height']), int(cur['width']), 3):

@@ -101,6 +101,21 @@ def index_maps(bvh, prim_perm, counts):
             'left': bvh['bvh_left_child'][inner], 'right': bvh['bvh_right_child'][inner]}
 
 
+def check_indices(name, idx, count):
+    """Reference primitive indices of kind ``name`` as a 1-D int64 array: integers, within [0, count), none twice.
+    A ValueError otherwise."""
+    idx = np.asarray(idx)
+    n = int(idx.size)
+    if idx.ndim != 1 or (n and not np.issubdtype(idx.dtype, np.integer)):
+        raise ValueError(f'{name}: indices must be a 1-D integer array')
+    idx = idx.astype(np.int64)
+    if n and (idx.min() < 0 or idx.max() >= count):
+        raise ValueError(f'{name}: an index is outside [0, {count})')
+    if np.unique(idx).size != n:
+        raise ValueError(f'{name}: an index is repeated')
+    return idx
+
+
 def check_edits(counts, spheres=None, quads=None, triangles=None):
     """update_primitives' arguments checked against the ByCode ``counts``: {type code: (int64 indices,
     (n, row floats) rows, (n, build floats) build records)} of the non-empty ones. A ValueError otherwise."""
@@ -110,15 +125,8 @@ def check_edits(counts, spheres=None, quads=None, triangles=None):
             continue
         name, count = k.name, counts[k.code]
         idx, rows, build = arg
-        idx = np.asarray(idx)
+        idx = check_indices(name, idx, count)
         n = int(idx.size)
-        if idx.ndim != 1 or (n and not np.issubdtype(idx.dtype, np.integer)):
-            raise ValueError(f'{name}: indices must be a 1-D integer array')
-        idx = idx.astype(np.int64)
-        if n and (idx.min() < 0 or idx.max() >= count):
-            raise ValueError(f'{name}: an index is outside [0, {count})')
-        if np.unique(idx).size != n:
-            raise ValueError(f'{name}: an index is repeated')
         rows, build = np.ascontiguousarray(rows, np.float32), np.ascontiguousarray(build, np.float32)
         if rows.size != n * k.row_floats or build.size != n * k.build_floats:
             raise ValueError(f'{name}: rows must be (n, {k.row_floats}) and build records (n, {k.build_floats}) f32')
@@ -131,6 +139,26 @@ def check_edits(counts, spheres=None, quads=None, triangles=None):
         if n:
             edits[k.code] = (idx, rows, build)
     return edits
+
+
+def current_edits(sa, lay, maps, indices):
+    """The edits that write back what the mirror holds: for ``indices`` ({type code: int64 reference indices})
+    ``check_edits``' form {type code: (indices, rows, build records)}, the rows the layout's own, the build records
+    from the mirror's arrays. The rest list of DeviceScene.set_tracks."""
+    out = {}
+    for t, idx in indices.items():
+        k = KINDS[t]
+        rows = np.ascontiguousarray(getattr(lay, k.rows)[maps['dev_of'][t][idx]], np.float32)
+        if t == PRIM_SPHERE:
+            build = rows.copy()
+        elif t == PRIM_QUAD:
+            build = np.ascontiguousarray(rows[:, k.build_columns])
+        else:
+            tr = sa.tris
+            build = np.concatenate([tr['triangle_v0'][idx], tr['triangle_v1'][idx], tr['triangle_v2'][idx]],
+                                   axis=1).astype(np.float32)
+        out[t] = (idx, rows, build)
+    return out
 
 
 def refresh_mirror(sa, lay, maps, edits, ref_nodes):
