@@ -1,7 +1,8 @@
 // material_check.cpp — the material-edit ABI's integer rules
-// (pt_material_math.hpp, the functions the kernel of pt_material.hip calls) run
-// on the CPU: a stand-alone host program, no HIP, no GPU. `make material_check`
-// builds it; tests/test_material_abi.py compares its output with
+// (pt_material_math.hpp and, for the leaf code, pt_scene_rows.hpp: the
+// functions the kernel of pt_material.hip calls) run on the CPU: a stand-alone
+// host program, no HIP, no GPU. `make material_check` builds it;
+// tests/test_material_abi.py compares its output with
 // scene_data.material_class and scene_data.leaf_code.
 //
 //   material_check classes flags.u32 out.u32
@@ -11,7 +12,7 @@
 //
 // Files are raw little-endian 4-byte words, one per case; the inputs of one
 // mode have the same length. classes: mat_class of every flags word. patch:
-// mat_patch_code of every (code, class). names: 1 where mat_code_names holds.
+// leaf_patch_class of every (code, class). names: 1 where leaf_code_names holds.
 // images: 1 where mat_image_ok holds. Exit 0 on success, 2 on bad arguments or
 // I/O.
 #include <stdint.h>
@@ -69,9 +70,9 @@ int main(int argc, char** argv) {
   std::vector<uint32_t> out(in[0].size());
   for (size_t i = 0; i < out.size(); ++i) {
     if (n_in == 2)
-      out[i] = mat_patch_code(in[0][i], in[1][i]);
+      out[i] = leaf_patch_class(in[0][i], in[1][i]);
     else if (n_in == 3)
-      out[i] = mat_code_names(in[0][i], (int32_t)in[1][i], (int32_t)in[2][i]) ? 1u : 0u;
+      out[i] = leaf_code_names(in[0][i], (int32_t)in[1][i], (int32_t)in[2][i]) ? 1u : 0u;
     else
       out[i] = images ? (mat_image_ok(in[0][i], num_images) ? 1u : 0u) : mat_class(in[0][i]);
   }

@@ -2,7 +2,9 @@
 // (pt_abi.hip, pt_denoise.hip, pt_guide.hip, pt_reproject.hip, pt_motion.hip,
 // pt_update.hip, pt_tree.hip, pt_validate.hip, pt_material.hip, pt_pose.hip).
 // Host only. The text of ptmi_last_error() and the render prologue are
-// pt_abi.hip's; the rest is inline.
+// pt_abi.hip's; the rest is inline. What only the calls that edit a resident
+// scene share (pt_update.hip, pt_pose.hip, pt_material.hip) is
+// pt_edit_lists.hpp's.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -29,6 +31,7 @@ inline int hip_result(hipError_t e) {
 }
 
 inline bool bad16(const void* p) { return !p || ((uintptr_t)p & 15u); }  // NULL or misaligned
+inline bool bad8(const void* p) { return !p || ((uintptr_t)p & 7u); }
 inline bool bad4(const void* p) { return !p || ((uintptr_t)p & 3u); }
 
 // Pixels of a width x height image, 0 for a size no image kernel takes

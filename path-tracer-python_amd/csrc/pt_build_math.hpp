@@ -530,7 +530,7 @@ PTMI_BLD_HD void build_finish(const BuildCtx& c, const BuildShared& sh, int32_t 
   }
 
 // ------------------------------------------------------------------ the packer
-constexpr int kPackNodeFloats = 20, kPackRefFloats = 12, kPackMatFloats = kMatFloats;
+constexpr int kPackNodeFloats = kNodeFloats, kPackRefFloats = kRefFloats, kPackMatFloats = kMatFloats;
 // f32 of a primitive row of include/ptmi.h by type code: sphere, triangle, quad
 PTMI_BLD_HD int pack_row_floats(int t) { return t == 0 ? 4 : t == 1 ? 12 : 16; }
 static_assert(2 * PTMI_BUILD_MAX_PRIMS - 1 <= 8 * kBuildLanes, "a lane counts eight nodes");

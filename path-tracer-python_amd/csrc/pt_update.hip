@@ -16,9 +16,11 @@
 //     faster on trees of a few thousand nodes, chosen by the caller.
 //   * upd_root: ref_nodes[0]'s box to the caller's float[6].
 //
-// The scene and topology checks and the launches of the refit and the root
-// copy are functions of their own (pt_update_launch.hpp): the pose ABI
-// (pt_pose.hip) runs the same step 2 after its own step 1.
+// The lists' head, the selection of a lane's entry, the skip rule and the
+// host checks of the lists are pt_edit_lists.hpp's, shared with the pose and
+// the material ABI (pt_pose.hip, pt_material.hip). The scene and topology
+// checks and the launches of the refit and the root copy are declared there
+// too: the pose ABI runs the same step 2 after its own step 1.
 //
 // The arithmetic is pt_update_math.hpp's, shared with update_check.cpp. A few
 // thousand lanes of min / max: no LDS, no cross-lane reads, nothing timed by
@@ -26,35 +28,28 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/ptmi_update.h"
-#include "pt_args.hpp"
-#include "pt_update_launch.hpp"
-#include "pt_update_math.hpp"
+#include "pt_edit_lists.hpp"
 
 namespace ptmi {
 
 constexpr int kUpdBlock = 256;
-constexpr int kRefFloats = 12;   // a ref_nodes row (include/ptmi.h)
-constexpr int kNodeFloats = 20;  // a nodes row
 
 // One list of edits as a kernel argument, with what its type fixes.
-struct UpdList {
-  const int32_t* prim;
-  const int32_t* leaf;
+struct UpdList : EditHead {
   const float* row;
   const float* build;
-  float* prims;      // the type's primitive array
-  int32_t count;
-  int32_t num_prims;
-  int32_t type;      // the type code of a leaf: 0 sphere, 1 triangle, 2 quad
+  float* prims;  // the type's primitive array
   int32_t row_floats, build_floats;
-};
 
-__device__ __forceinline__ void upd_store_box(float* ref, const UpdBox& b) {
-  for (int k = 0; k < 3; ++k) {
-    ref[k] = b.mn[k];
-    ref[4 + k] = b.mx[k];
+  void set_payload(const ptmi_update_list* a, int k, float* rows, int32_t) {
+    row = a ? a->row : nullptr;
+    build = a ? a->build : nullptr;
+    prims = rows;
+    row_floats = kEditKinds[k].row_floats;
+    build_floats = k == 0 ? 4 : 9;
   }
-}
+  bool bad_payload() const { return bad4(row) || bad4(build) || bad4(prims); }
+};
 
 __device__ __forceinline__ UpdBox upd_load_box(const float* ref) {
   UpdBox b;
@@ -65,33 +60,20 @@ __device__ __forceinline__ UpdBox upd_load_box(const float* ref) {
   return b;
 }
 
-__global__ __launch_bounds__(kUpdBlock) void upd_leaves(UpdList s, UpdList q, UpdList t, float* __restrict__ ref_nodes,
-                                                        int32_t num_bvh_nodes) {
-  int32_t i = (int32_t)(blockIdx.x * (uint32_t)kUpdBlock + threadIdx.x);
-  UpdList e = s;
-  if (i >= s.count) {
-    i -= s.count;
-    e = q;
-    if (i >= q.count) {
-      i -= q.count;
-      e = t;
-      if (i >= t.count) return;
-    }
-  }
-  const int32_t p = e.prim[i], leaf = e.leaf[i];
-  if (p < 0 || p >= e.num_prims || leaf < 0 || leaf >= num_bvh_nodes) return;
-  float* ref = ref_nodes + (size_t)leaf * kRefFloats;
-  // leaf code 0x80000000 | type << 28 | class << 25 | index: this primitive's leaf?
-  const uint32_t code = __float_as_uint(ref[9]);
-  if ((code >> 28) != (8u | (uint32_t)e.type) || (code & 0x1ffffffu) != (uint32_t)p) return;
+__global__ __launch_bounds__(kEditBlock) void upd_leaves(UpdList s, UpdList q, UpdList t, float* __restrict__ ref_nodes,
+                                                         int32_t num_bvh_nodes) {
+  int32_t i = (int32_t)(blockIdx.x * (uint32_t)kEditBlock + threadIdx.x);
+  UpdList e;
+  EditTarget tg;
+  if (!edit_select(s, q, t, e, i) || !edit_target(e, i, ref_nodes, num_bvh_nodes, tg)) return;
   const float* row = e.row + (size_t)i * e.row_floats;
-  float* dst = e.prims + (size_t)p * e.row_floats;
+  float* dst = e.prims + (size_t)tg.prim * e.row_floats;
   for (int k = 0; k < e.row_floats; ++k) dst[k] = row[k];
   const float* rec = e.build + (size_t)i * e.build_floats;
   float b9[9];
   for (int k = 0; k < 9; ++k) b9[k] = (k < e.build_floats) ? rec[k] : 0.0f;
   const UpdBox box = e.type == 0 ? upd_sphere_box(b9) : e.type == 2 ? upd_quad_box(b9) : upd_tri_box(b9);
-  upd_store_box(ref, box);
+  upd_store_box(tg.ref, box);
 }
 
 // Internal node i: the union of its children's boxes into ref_nodes[i], their
@@ -151,22 +133,7 @@ __global__ void upd_root(const float* __restrict__ ref_nodes, float* __restrict_
   if (k < 6) root_box[k] = ref_nodes[k < 3 ? k : k + 1];
 }
 
-static bool upd_fill(UpdList& d, const ptmi_update_list* s, const float* prims, int32_t num_prims, int32_t type,
-                     int32_t row_floats, int32_t build_floats) {
-  d.prim = s ? s->prim : nullptr;
-  d.leaf = s ? s->leaf : nullptr;
-  d.row = s ? s->row : nullptr;
-  d.build = s ? s->build : nullptr;
-  d.prims = const_cast<float*>(prims);
-  d.count = s ? s->count : 0;
-  d.num_prims = num_prims;
-  d.type = type;
-  d.row_floats = row_floats;
-  d.build_floats = build_floats;
-  return d.count >= 0 && d.count <= num_prims;
-}
-
-// ---- the host half shared with the pose ABI (pt_update_launch.hpp)
+// ---- the refit step shared with the pose ABI (pt_edit_lists.hpp)
 int upd_check_scene(const ptmi_scene_view* scene, const char* what) {
   if (!scene) return fail(PTMI_EINVAL, "%s: scene is NULL", what);
   if (scene->n_inner < 0 || scene->num_bvh_nodes < 0 || scene->num_spheres < 0 || scene->num_quads < 0 ||
@@ -235,26 +202,16 @@ int ptmi_update_primitives(const ptmi_scene_view* scene, const ptmi_update_list*
                            const ptmi_update_list* quads, const ptmi_update_list* tris,
                            const ptmi_update_topology* topo, float* root_box, void* stream) {
   if (int rc = upd_check_scene(scene, "update")) return rc;
-  UpdList s, q, t;
-  if (!upd_fill(s, spheres, scene->spheres, scene->num_spheres, 0, 4, 4))
-    return fail(PTMI_EINVAL, "update: sphere count negative or above num_spheres");
-  if (!upd_fill(q, quads, scene->quads, scene->num_quads, 2, 16, 9))
-    return fail(PTMI_EINVAL, "update: quad count negative or above num_quads");
-  if (!upd_fill(t, tris, scene->tris, scene->num_triangles, 1, 12, 9))
-    return fail(PTMI_EINVAL, "update: triangle count negative or above num_triangles");
-  const struct {
-    const UpdList& l;
-    const char* name;
-  } lists[3] = {{s, "sphere"}, {q, "quad"}, {t, "triangle"}};
-  for (const auto& e : lists)
-    if (e.l.count > 0 && (bad4(e.l.prim) || bad4(e.l.leaf) || bad4(e.l.row) || bad4(e.l.build) || bad4(e.l.prims)))
-      return fail(PTMI_EINVAL, "update: a %s list pointer is NULL/misaligned", e.name);
-  const int64_t n_edits = (int64_t)s.count + q.count + t.count;
+  UpdList l[3];
+  const ptmi_update_list* const abi[3] = {spheres, quads, tris};
+  if (int rc = edit_fill("update", scene, abi, l)) return rc;
+  if (int rc = edit_check_pointers("update", l)) return rc;
+  const int64_t n_edits = edit_total(l);
   if (int rc = upd_check_tree(scene, topo, root_box, n_edits, "update")) return rc;
   if (scene->num_bvh_nodes == 0) return PTMI_OK;
   if (n_edits > 0)
-    hipLaunchKernelGGL(upd_leaves, dim3((unsigned)((n_edits + kUpdBlock - 1) / kUpdBlock)), dim3(kUpdBlock), 0,
-                       (hipStream_t)stream, s, q, t, const_cast<float*>(scene->ref_nodes), scene->num_bvh_nodes);
+    hipLaunchKernelGGL(upd_leaves, edit_grid(n_edits), dim3(kEditBlock), 0, (hipStream_t)stream, l[0], l[1], l[2],
+                       const_cast<float*>(scene->ref_nodes), scene->num_bvh_nodes);
   upd_refit_launch(scene, topo, root_box, stream);
   return hip_result(hipGetLastError());
 }

@@ -31,6 +31,12 @@ def _stream_ptr(stream=None, device=None):
     return C.c_void_p(_stream_or_current(stream, device).cuda_stream)
 
 
+def _list_args(cls, lists):
+    """A call's three list arguments in storage order from its ``{type code: (pointers..., count)}`` tuples:
+    ``byref`` of the ctypes list ``cls``, None for a kind that is missing or empty."""
+    return [C.byref(cls(*e)) if e is not None and e[-1] else None for e in (lists.get(k.code) for k in STORAGE)]
+
+
 def require_gpu():
     if not torch.cuda.is_available():
         raise _lib.PtmiError('no GPU visible: the MI355X integrator has no CPU fallback')
@@ -155,6 +161,40 @@ class DeviceScene:
                     level_end=(C.c_int32 * max(1, level_end.size))(*level_end.tolist()), n_levels=int(level_end.size),
                     root=torch.zeros(6, dtype=torch.float32, device=dev))
 
+    def _topology(self, st, flags):
+        """The ptmi_update_topology of a call: ``flags`` None is update.refit_flags' choice for the tree's size."""
+        if flags is None:
+            flags = update.refit_flags(self.layout.n_inner, st['n_levels'])
+        return update.UpdateTopology(st['order'].data_ptr() if st['order'] is not None else None,
+                                     st['slot'].data_ptr() if st['slot'] is not None else None,
+                                     st['level_end'], st['n_levels'], int(flags))
+
+    def _pack_edits(self, edits, dtype=np.float32, stream=None):
+        """``{type code: (reference indices, payload arrays...)}`` on the device, uploaded under ``stream``: one
+        int32 tensor (per kind the device rows, then the leaves) and one ``dtype`` tensor (per kind its arrays in
+        argument order). Returns the ``{type code: (prim ptr, leaf ptr, payload ptrs..., n)}`` the ``*_call``
+        methods take, and the tensors to keep alive."""
+        st = self._update_state()
+        ints, payload, lists, ni, npay = [], [], {}, 0, 0
+        for t, (idx, *arrays) in edits.items():
+            n = idx.size
+            ints += [st['dev_of'][t][idx].astype(np.int32), st['leaf_of'][t][idx].astype(np.int32)]
+            starts = []
+            for a in arrays:
+                payload.append(a.reshape(-1))
+                starts.append(npay)
+                npay += a.size
+            lists[t] = (ni, ni + n, *starts, n)  # element offsets, made pointers below
+            ni += 2 * n
+        if not ints:
+            return lists, ()
+        with torch.cuda.device(self.device), torch.cuda.stream(_stream_or_current(stream, self.device)):
+            ti = torch.from_numpy(np.concatenate(ints)).to(self.device)  # the uploads precede the kernel on its stream
+            tp = torch.from_numpy(np.concatenate(payload).astype(dtype, copy=False)).to(self.device)
+        pi, pp, size = ti.data_ptr(), tp.data_ptr(), tp.element_size()  # torch allocations are 8-B aligned
+        return {t: (pi + 4 * a, pi + 4 * b, *(pp + size * c for c in pay), n)
+                for t, (a, b, *pay, n) in lists.items()}, (ti, tp)
+
     def update_call(self, lists, stream=None, flags=None):
         """ptmi_update_primitives on this scene: ``lists`` maps a primitive type
         code to (prim ptr, leaf ptr, row ptr, build ptr, count) of edits already
@@ -162,14 +202,8 @@ class DeviceScene:
         update.ONE_GROUP: the single-workgroup refit), by default
         update.refit_flags' choice for the tree's size. Asynchronous; the host
         mirror and the view are not refreshed (update_primitives does both)."""
-        st = self._update_state()
-        if flags is None:
-            flags = update.refit_flags(self.layout.n_inner, st['n_levels'])
-        arg = [C.byref(update.UpdateList(*e)) if e is not None and e[4] else None
-               for e in (lists.get(k.code) for k in STORAGE)]
-        topo = update.UpdateTopology(st['order'].data_ptr() if st['order'] is not None else None,
-                                     st['slot'].data_ptr() if st['slot'] is not None else None,
-                                     st['level_end'], st['n_levels'], int(flags))
+        st, arg = self._update_state(), _list_args(update.UpdateList, lists)
+        topo = self._topology(st, flags)
         with torch.cuda.device(self.device):
             _lib.check(update.load().ptmi_update_primitives(self.view, arg[0], arg[1], arg[2], C.byref(topo),
                                                             st['root'].data_ptr(), _stream_ptr(stream, self.device)),
@@ -197,32 +231,12 @@ class DeviceScene:
         if self._tracks is not None and any(np.intersect1d(idx, self._tracks['indices'].get(t, ())).size
                                             for t, (idx, _, _) in edits.items()):
             self._tracks = None
-        self._upload_edits(st, edits, stream, flags)
+        lists, _keep = self._pack_edits(edits, stream=stream)
+        self.update_call(lists, stream, flags)
         _stream_or_current(stream, self.device).synchronize()
         update.refresh_mirror(self.arrays, self.layout, st, edits,
                               self.t_ref_nodes.cpu().numpy() if self.arrays.num_bvh_nodes else None)
         self._set_tree(self.layout)
-
-    def _upload_edits(self, st, edits, stream, flags):
-        """The checked edits to the device in one int and one float tensor, and update_call on them."""
-        self.update_call(self._edit_lists(st, edits)[0], stream, flags)
-
-    def _edit_lists(self, st, edits):
-        """The checked edits on the device in one int and one float tensor: (update_call's lists, the tensors)."""
-        ints, floats, lists, ni, nf = [], [], {}, 0, 0
-        for t, (idx, rows, build) in edits.items():
-            n = idx.size
-            ints += [st['dev_of'][t][idx].astype(np.int32), st['leaf_of'][t][idx].astype(np.int32)]
-            floats += [rows.reshape(-1), build.reshape(-1)]
-            lists[t] = (ni, ni + n, nf, nf + rows.size, n)  # element offsets, made pointers below
-            ni, nf = ni + 2 * n, nf + rows.size + build.size
-        if ints:
-            ti = torch.from_numpy(np.concatenate(ints)).to(self.device)
-            tf = torch.from_numpy(np.concatenate(floats)).to(self.device)
-            pi, pf = ti.data_ptr(), tf.data_ptr()
-            lists = {t: (pi + 4 * a, pi + 4 * b, pf + 4 * c, pf + 4 * d, n) for t, (a, b, c, d, n) in lists.items()}
-            return lists, (ti, tf)
-        return lists, ()
 
     # ------------------------------------------------ poses of moving primitives (ptmi.pose)
     def _require_unposed(self):
@@ -249,22 +263,9 @@ class DeviceScene:
         st = self._update_state()
         (t0, t1), _ = pose_mod.check_shutter(t_range, 1)
         tracks = pose_mod.check_tracks(counts_by_code(self.layout), spheres, quads, triangles)
-        ints, recs, lists, ni, nr = [], [], {}, 0, 0
-        for t, (idx, rec) in tracks.items():
-            n = idx.size
-            ints += [st['dev_of'][t][idx].astype(np.int32), st['leaf_of'][t][idx].astype(np.int32)]
-            recs.append(rec.reshape(-1))
-            lists[t] = (ni, ni + n, nr, n)  # element offsets, made pointers below
-            ni, nr = ni + 2 * n, nr + rec.size
-        keep = ()
-        if ints:
-            ti = torch.from_numpy(np.concatenate(ints)).to(self.device)
-            tr = torch.from_numpy(np.concatenate(recs)).to(self.device)  # f64: torch allocations are 8-B aligned
-            pi, pr = ti.data_ptr(), tr.data_ptr()
-            lists = {t: (pi + 4 * a, pi + 4 * b, pr + 8 * c, n) for t, (a, b, c, n) in lists.items()}
-            keep = (ti, tr)
+        lists, keep = self._pack_edits(tracks, np.float64)
         indices = {t: idx for t, (idx, _) in tracks.items()}
-        rest, rest_keep = self._edit_lists(st, update.current_edits(self.arrays, self.layout, st, indices))
+        rest, rest_keep = self._pack_edits(update.current_edits(self.arrays, self.layout, st, indices))
         self._tracks = {'lists': lists, 'rest': rest, 'keep': keep + rest_keep, 'indices': indices,
                         't_range': (t0, t1), 'shell': 0}
         self._tracks['shell'] = self._posed_shell(st, indices, t0, t1)
@@ -306,14 +307,8 @@ class DeviceScene:
         t = float(t)
         if not tr['t_range'][0] <= t <= tr['t_range'][1]:
             raise ValueError(f'pose: t = {t!r} is outside the tracks\' t_range {tr["t_range"]}')
-        st = self._update_state()
-        if flags is None:
-            flags = update.refit_flags(self.layout.n_inner, st['n_levels'])
-        arg = [C.byref(pose_mod.PoseList(*e)) if e is not None and e[3] else None
-               for e in (tr['lists'].get(k.code) for k in STORAGE)]
-        topo = update.UpdateTopology(st['order'].data_ptr() if st['order'] is not None else None,
-                                     st['slot'].data_ptr() if st['slot'] is not None else None,
-                                     st['level_end'], st['n_levels'], int(flags))
+        st, arg = self._update_state(), _list_args(pose_mod.PoseList, tr['lists'])
+        topo = self._topology(st, flags)
         with torch.cuda.device(self.device):
             _lib.check(pose_mod.load().ptmi_pose_primitives(self.view, arg[0], arg[1], arg[2], t, C.byref(topo),
                                                             st['root'].data_ptr(), _stream_ptr(stream, self.device)),
@@ -356,9 +351,7 @@ class DeviceScene:
         code to (prim ptr, leaf ptr, row ptr, count) of edits already on the
         device. Asynchronous; the host mirror and the view are not refreshed
         (update_materials does both)."""
-        st = self._update_state()
-        arg = [C.byref(material.MaterialList(*e)) if e is not None and e[3] else None
-               for e in (lists.get(k.code) for k in STORAGE)]
+        st, arg = self._update_state(), _list_args(material.MaterialList, lists)
         with torch.cuda.device(self.device):
             _lib.check(material.load().ptmi_update_materials(self.view, arg[0], arg[1], arg[2],
                                                              st['slot'].data_ptr() if st['slot'] is not None else None,
@@ -387,19 +380,7 @@ class DeviceScene:
         st = self._update_state()
         edits = material.check_edits(counts_by_code(self.layout), len(self.layout.img_w), spheres, quads, triangles)
         s = _stream_or_current(stream, self.device)
-        ints, floats, lists, ni, nf = [], [], {}, 0, 0
-        for t, (idx, rows) in edits.items():
-            n = idx.size
-            ints += [st['dev_of'][t][idx].astype(np.int32), st['leaf_of'][t][idx].astype(np.int32)]
-            floats.append(rows.reshape(-1))
-            lists[t] = (ni, ni + n, nf, n)  # element offsets, made pointers below
-            ni, nf = ni + 2 * n, nf + rows.size
-        if ints:
-            with torch.cuda.device(self.device), torch.cuda.stream(s):  # the uploads precede the kernel on its stream
-                ti = torch.from_numpy(np.concatenate(ints)).to(self.device)
-                tf = torch.from_numpy(np.concatenate(floats)).to(self.device)
-            pi, pf = ti.data_ptr(), tf.data_ptr()
-            lists = {t: (pi + 4 * a, pi + 4 * b, pf + 4 * c, n) for t, (a, b, c, n) in lists.items()}
+        lists, _keep = self._pack_edits(edits, stream=s)
         self.material_call(lists, s)
         s.synchronize()
         material.refresh_mirror(self.arrays, self.layout, st, edits, self._pack[0])

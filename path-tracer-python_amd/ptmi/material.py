@@ -18,6 +18,7 @@ import numpy as np
 from . import _lib
 from .scene_data import (KINDS, LEAF_INDEX_BITS, MAT_FLOATS, NODE_BYTES, STORAGE, mat_bases, mat_flags,
                          material_class, shell_hint, unpack_mats)
+from .update import check_indices
 
 MATERIAL_VERSION = 1  # PTMI_MATERIAL_VERSION of include/ptmi_material.h
 CLASS_MASK = 7 << LEAF_INDEX_BITS  # the material class of a leaf code, bits 25 - 27
@@ -56,15 +57,8 @@ def check_edits(counts, num_images, spheres=None, quads=None, triangles=None):
             continue
         name, count = k.name, counts[k.code]
         idx, rows = arg
-        idx = np.asarray(idx)
+        idx = check_indices(name, idx, count)
         n = int(idx.size)
-        if idx.ndim != 1 or (n and not np.issubdtype(idx.dtype, np.integer)):
-            raise ValueError(f'{name}: indices must be a 1-D integer array')
-        idx = idx.astype(np.int64)
-        if n and (idx.min() < 0 or idx.max() >= count):
-            raise ValueError(f'{name}: an index is outside [0, {count})')
-        if np.unique(idx).size != n:
-            raise ValueError(f'{name}: an index is repeated')
         rows = np.ascontiguousarray(rows, np.float32)
         if rows.size != n * MAT_FLOATS:
             raise ValueError(f'{name}: rows must be (n, {MAT_FLOATS}) f32')

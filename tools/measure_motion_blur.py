@@ -98,12 +98,11 @@ def pose_timing(name, out, tracked):
         return times[k[0] % len(times)]
 
     # the same posed records as an update whose lists are already on the device
-    st = ds._update_state()
     from ptmi import update
     lists = []
     for tt in times:
         edits = update.check_edits(sd.counts_by_code(ds.layout), *pose.posed_records(tracks, tt))
-        lists.append(ds._edit_lists(st, edits))
+        lists.append(ds._pack_edits(edits))
     n = sum(len(v) for v in tracks.values())
 
     def update_call():
