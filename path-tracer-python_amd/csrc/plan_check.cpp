@@ -12,6 +12,9 @@
 // plan's regions lie inside the unlisted workspace and its decode reaches
 // every (listed tile, sample, lane) once and nothing else. Three plans are
 // pinned literally: the fields that set speed and that no image test sees.
+// The decodes it runs are the kernels' own host/device functions (fdiv,
+// frame_row, frame_index, tile_pixel, decode_item); only the
+// megakernel's unit decode is restated here (locate_host).
 #include <stdint.h>
 #include <stdio.h>
 
@@ -24,14 +27,14 @@ using namespace ptmi;
 
 static int g_failed = 0;
 static char g_ctx[160] = "";
+#define PT_STR2(x) #x
+#define PT_STR(x) PT_STR2(x)
 #define CHECK(c)                                                            \
   do {                                                                      \
     if (!(c)) {                                                             \
       if (++g_failed <= 40) printf("FAILED %s: %s  [%s]\n", #c, g_ctx, __FILE__ ":" PT_STR(__LINE__)); \
     }                                                                       \
   } while (0)
-#define PT_STR2(x) #x
-#define PT_STR(x) PT_STR2(x)
 
 // A DevFrame as pt_abi.hip's to_dev_frame fills it (the fields the plans read).
 static DevFrame frame(int32_t width, int32_t height, int32_t x0, int32_t y0, int32_t w, int32_t h, int32_t band_rows = 1,
@@ -65,6 +68,20 @@ static std::vector<Case> frames() {
   };
 }
 
+// DevFrame::n_rows against the kernels' frame_row: strictly increasing image
+// rows of the window, each in a band with the frame's offset, and -1 from
+// n_rows on.
+static void check_frame(const DevFrame& fr) {
+  int32_t prev = -1;
+  for (int32_t lr = 0; lr < fr.n_rows; ++lr) {
+    const int32_t row = frame_row(fr, lr);
+    CHECK(row > prev && row >= fr.y0 && row < fr.y0 + fr.h);
+    CHECK(((row - fr.y0) / fr.band_rows) % fr.band_stride == fr.band_offset);
+    prev = row;
+  }
+  for (int32_t lr = fr.n_rows; lr < fr.n_rows + 3 * fr.band_rows; ++lr) CHECK(frame_row(fr, lr) == -1);
+}
+
 // A workspace address that is never dereferenced.
 static char* const kBase = (char*)(uintptr_t)0x7000000000ull;
 constexpr int kPerCu = 20, kNcu = 256;  // vol2's occupancy on a 256-CU MI355X
@@ -79,30 +96,32 @@ static void check_tile_grid(const DevFrame& fr) {
   // a banded frame's tile never straddles two bands
   if (fr.band_stride > 1) CHECK(fr.band_rows % th == 0 || th == 1);
   if (fr.band_stride <= 1) CHECK(th == 8);
-  // every pixel of the frame is lane p of exactly one tile (tile_pixel, pt_adaptive.hip)
+  // every pixel of the frame is lane p of exactly one tile (the kernels' tile_pixel, pt_mk_plan.hpp)
   if ((int64_t)fr.w * fr.n_rows <= (1 << 20)) {
     std::vector<uint8_t> seen((size_t)fr.w * fr.n_rows, 0);
     for (int32_t t = 0; t < g.ntiles; ++t)
       for (int32_t p = 0; p < 64; ++p) {
-        const int32_t ty = t / g.tiles_x, tx = t - ty * g.tiles_x;
-        const int32_t col = (tx << g.tw_log2) + (p & (tw - 1)), lr = (ty << (6 - g.tw_log2)) + (p >> g.tw_log2);
-        if (col < fr.w && lr < fr.n_rows) ++seen[(size_t)lr * fr.w + col];
+        int32_t col, lr;
+        if (!tile_pixel(fr, g, t, p, col, lr)) continue;
+        CHECK(col >= 0 && lr >= 0 && col / tw == t % g.tiles_x && lr / th == t / g.tiles_x && col % tw + (lr % th) * tw == p);
+        ++seen[(size_t)lr * fr.w + col];
       }
     CHECK(std::all_of(seen.begin(), seen.end(), [](uint8_t c) { return c == 1; }));
   }
 }
 
 // ------------------------------------------------------------------ megakernel
-// COPY of the device code's unit decode (fdiv, pt_device.hpp; locate() of
-// mk_render_kernel, pt_megakernel.hip), restated on the host because kernel
-// code is not shared with this program. A unit is item >> 6.
-static uint32_t fdiv_host(uint32_t n, const FastDiv& f) { return (uint32_t)(((uint64_t)n * f.m) >> f.sh); }
+// COPY of the persistent branch of locate() of mk_render_kernel
+// (pt_megakernel.hip), the one decode still restated here: as a host/device
+// function it compiled to other device code in the unlisted staged kernels
+// (DESIGN.md §3), so it stays in its kernel. Its pieces (fdiv, tile_col0,
+// tile_row0) are the kernel's own. A unit is item >> 6.
 struct Unit {
   int32_t col, row, s;  // tile origin (window column, local row), sample of the batch
 };
 static Unit locate_host(const DevFrame& fr, const MkWork& wk, uint32_t v, const std::vector<int32_t>* list) {
-  const uint32_t sh = fdiv_host(v, wk.by_len), j = v - sh * (uint32_t)wk.shard_len;
-  const uint32_t tq = fdiv_host(j, wk.by_nb);
+  const uint32_t sh = fdiv(v, wk.by_len), j = v - sh * (uint32_t)wk.shard_len;
+  const uint32_t tq = fdiv(j, wk.by_nb);
   uint32_t t = tq * (uint32_t)kMkShards + sh;
   const int32_t s = (int32_t)(j - tq * (uint32_t)wk.nb);
   if (list) {
@@ -110,8 +129,8 @@ static Unit locate_host(const DevFrame& fr, const MkWork& wk, uint32_t v, const 
     if (id >= (uint32_t)wk.ntiles) return Unit{0, fr.n_rows, s};
     t = id;
   }
-  const uint32_t ty = fdiv_host(t, wk.by_tiles_x);
-  return Unit{(int32_t)(t - ty * (uint32_t)wk.tiles_x) << wk.tw_log2, (int32_t)ty << (6 - wk.tw_log2), s};
+  const uint32_t ty = fdiv(t, wk.by_tiles_x);
+  return Unit{tile_col0(wk.tw_log2, (int32_t)(t - ty * (uint32_t)wk.tiles_x)), tile_row0(wk.tw_log2, (int32_t)ty), s};
 }
 
 // Every (tile, sample) of the launch is exactly one unit, every other unit
@@ -192,18 +211,17 @@ struct Region {
   const char* what;
 };
 
-// COPY of decode_item (pt_wavefront.hip), restated on the host like the
-// megakernel's: the staging slot srel * npix + p of work item k, or -1 for an
-// item outside the frame or past the batch.
-static int64_t wf_slot_host(const DevFrame& fr, const WfBufs& wb, uint32_t k) {
-  const uint32_t per = 64u * (uint32_t)wb.csamp;
-  const uint32_t c = fdiv_host(k, wb.by_per), j = k - c * per;
-  const uint32_t blk = fdiv_host(c, wb.by_nsq), q = c - blk * (uint32_t)wb.nsq;
-  const int32_t qy = (int32_t)fdiv_host(q, wb.by_sqx), qx = (int32_t)q - qy * wb.sq_x;
-  const int32_t lx = qx * 8 + (int32_t)(j & 7u), lr = qy * 8 + (int32_t)((j >> 3) & 7u);
-  const int32_t srel = (int32_t)blk * wb.csamp + (int32_t)(j >> 6);
-  if (!(lx < fr.w && lr < fr.n_rows && srel < wb.batch)) return -1;
-  return (int64_t)srel * wb.npix + (lr * fr.w + lx);
+// The staging slot srel * npix + p of work item k as the kernels' decode_item
+// (pt_wf_plan.hpp) gives it, or -1 for an item outside the frame or past the
+// batch. A valid item's image pixel is what plain arithmetic gives for its
+// (local row, window column), and both frame_index overloads agree.
+static int64_t wf_slot(const DevFrame& fr, const WfBufs& wb, const Item& it) {
+  if (!it.valid) return -1;
+  const int32_t lr = it.p / fr.w, col = it.p % fr.w;
+  CHECK(it.px == fr.x0 + col && it.py == frame_row(fr, lr) && it.py >= fr.y0 && it.py < fr.y0 + fr.h);
+  const size_t pix = (size_t)it.py * (size_t)fr.width + (size_t)it.px;
+  CHECK(frame_index(fr, lr, col) == pix && frame_index(fr, it.p) == pix);
+  return (int64_t)it.srel * wb.npix + it.p;
 }
 
 // Every (sample, pixel) of the batch is exactly one work item, so every
@@ -217,37 +235,27 @@ static void check_wf_cover(const DevFrame& fr, const WfBufs& wb) {
       const int32_t lr = (int32_t)(q / (uint32_t)wb.sq_x) * 8 + (int32_t)((j >> 3) & 7u);
       const int32_t srel = (int32_t)(c / (uint32_t)wb.nsq) * wb.csamp + (int32_t)(j >> 6);
       const bool in = lx < fr.w && lr < fr.n_rows && srel < wb.batch;
-      CHECK(wf_slot_host(fr, wb, k) == (in ? (int64_t)srel * wb.npix + (lr * fr.w + lx) : -1));
+      CHECK(wf_slot(fr, wb, decode_item(fr, wb, WfList<false>{}, k)) == (in ? (int64_t)srel * wb.npix + (lr * fr.w + lx) : -1));
     }
     return;
   }
   std::vector<uint8_t> seen((size_t)wb.npix * wb.batch, 0);
   for (uint32_t k = 0; k < (uint32_t)wb.nitems; ++k) {
-    const int64_t slot = wf_slot_host(fr, wb, k);
+    const int64_t slot = wf_slot(fr, wb, decode_item(fr, wb, WfList<false>{}, k));
     CHECK(slot < (int64_t)seen.size());
     if (slot >= 0 && slot < (int64_t)seen.size()) ++seen[(size_t)slot];
   }
   CHECK(std::all_of(seen.begin(), seen.end(), [](uint8_t c) { return c == 1; }));
 }
 
-// COPY of the LISTED decode_item (pt_wavefront.hip; WfList<true> holds the
-// list, the grid's tile count and tw_log2), restated on the host.
-static int64_t wf_listed_slot_host(const DevFrame& fr, const WfBufs& wb, const std::vector<int32_t>& list,
-                                   const TileGrid& g, uint32_t k) {
-  const uint32_t per = 64u * (uint32_t)wb.csamp;
-  const uint32_t c = fdiv_host(k, wb.by_per), j = k - c * per;
-  const uint32_t blk = fdiv_host(c, wb.by_nsq), v = c - blk * (uint32_t)wb.nsq;
-  if (v >= list.size()) return -2;  // (never: the device would read past the list)
-  const int32_t id = list[v];
-  const bool in_grid = (uint32_t)id < (uint32_t)g.ntiles;
-  const uint32_t t = in_grid ? (uint32_t)id : 0u;
-  const int32_t ty = (int32_t)fdiv_host(t, wb.by_sqx), tx = (int32_t)t - ty * wb.sq_x;
-  const uint32_t lane = j & 63u;
-  const int32_t lx = (tx << g.tw_log2) + (int32_t)(lane & ((1u << g.tw_log2) - 1u));
-  const int32_t lr = ty * (64 >> g.tw_log2) + (int32_t)(lane >> g.tw_log2);
-  const int32_t srel = (int32_t)blk * wb.csamp + (int32_t)(j >> 6);
-  if (!(in_grid && lx < fr.w && lr < fr.n_rows && srel < wb.batch)) return -1;
-  return (int64_t)srel * wb.npix + (lr * fr.w + lx);
+// The same through the LISTED decode_item. -2: the plan's nsq exceeds the
+// list, so the device would read past it (never: nsq is n_list). The guard
+// compares nsq's range with list.size() by plain division before the call; it
+// does not look at the decode's own v.
+static int64_t wf_listed_slot(const DevFrame& fr, const WfBufs& wb, const std::vector<int32_t>& list,
+                              const TileGrid& g, uint32_t k) {
+  if ((k / (64u * (uint32_t)wb.csamp)) % (uint32_t)wb.nsq >= list.size()) return -2;
+  return wf_slot(fr, wb, decode_item(fr, wb, WfList<true>{list.data(), g.ntiles, g.tw_log2}, k));
 }
 
 // The listed decode reaches every (listed tile, sample, lane) inside the frame
@@ -266,14 +274,14 @@ static void check_wf_listed_cover(const DevFrame& fr, const WfBufs& wb, const st
     return lx < fr.w && lr < fr.n_rows && srel < wb.batch ? (int64_t)srel * wb.npix + ((int64_t)lr * fr.w + lx) : -1;
   };
   if (wb.nitems > (1 << 23) || (int64_t)wb.npix * wb.batch > (1ll << 26)) {
-    for (uint32_t k = 0; k < (uint32_t)wb.nitems; k += 4099) CHECK(wf_listed_slot_host(fr, wb, list, g, k) == plain(k));
+    for (uint32_t k = 0; k < (uint32_t)wb.nitems; k += 4099) CHECK(wf_listed_slot(fr, wb, list, g, k) == plain(k));
     for (int64_t k = (int64_t)wb.nitems - 64; k < wb.nitems; ++k)
-      if (k >= 0) CHECK(wf_listed_slot_host(fr, wb, list, g, (uint32_t)k) == plain((uint32_t)k));
+      if (k >= 0) CHECK(wf_listed_slot(fr, wb, list, g, (uint32_t)k) == plain((uint32_t)k));
     return;
   }
   std::vector<uint8_t> seen((size_t)wb.npix * wb.batch, 0), want(seen.size(), 0);
   for (uint32_t k = 0; k < (uint32_t)wb.nitems; ++k) {
-    const int64_t slot = wf_listed_slot_host(fr, wb, list, g, k);
+    const int64_t slot = wf_listed_slot(fr, wb, list, g, k);
     CHECK(slot >= -1 && slot < (int64_t)seen.size());
     if (slot >= 0 && slot < (int64_t)seen.size()) ++seen[(size_t)slot];
   }
@@ -405,6 +413,8 @@ int main() {
   int plans = 0;
   for (const Case& c : frames()) {
     const DevFrame& fr = c.fr;
+    snprintf(g_ctx, sizeof g_ctx, "%s: frame rows and pixels", c.name);
+    check_frame(fr);
     snprintf(g_ctx, sizeof g_ctx, "%s: tile grid", c.name);
     check_tile_grid(fr);
     const int64_t mk_max = mk_max_batch(fr), wf_max = wf_max_batch(fr);

@@ -28,10 +28,7 @@ namespace ptmi {
 __global__ __launch_bounds__(kBlock) void clear_kernel(DevFrame fr, float* __restrict__ accum) {
   const int32_t npix = fr.w * fr.n_rows;
   for (int32_t i = (int32_t)(blockIdx.x * kBlock + threadIdx.x); i < npix; i += (int32_t)(gridDim.x * kBlock)) {
-    int32_t lr = i / fr.w;
-    int32_t px = fr.x0 + (i - lr * fr.w);
-    int32_t py = frame_row(fr, lr);
-    float* p = accum + 3 * ((size_t)py * (size_t)fr.width + (size_t)px);
+    float* p = accum + 3 * frame_index(fr, i);
     p[0] = 0.0f;
     p[1] = 0.0f;
     p[2] = 0.0f;
@@ -56,10 +53,7 @@ __global__ __launch_bounds__(kBlock) void tonemap_kernel(const float* __restrict
 __global__ __launch_bounds__(kBlock) void stats_clear_kernel(DevFrame fr, float4* __restrict__ stats) {
   const int32_t npix = fr.w * fr.n_rows;
   for (int32_t i = (int32_t)(blockIdx.x * kBlock + threadIdx.x); i < npix; i += (int32_t)(gridDim.x * kBlock)) {
-    int32_t lr = i / fr.w;
-    int32_t px = fr.x0 + (i - lr * fr.w);
-    int32_t py = frame_row(fr, lr);
-    stats[(size_t)py * (size_t)fr.width + (size_t)px] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    stats[frame_index(fr, i)] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
   }
 }
 

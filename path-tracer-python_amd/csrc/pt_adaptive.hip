@@ -18,16 +18,6 @@
 
 namespace ptmi {
 
-// Lane p of tile t -> the pixel's column in the window and its local row (as
-// bind() of mk_render_kernel); false outside the frame.
-__device__ __forceinline__ bool tile_pixel(const DevFrame& fr, const TileGrid& g, int32_t t, int32_t p, int32_t& col,
-                                           int32_t& lr) {
-  const int32_t ty = t / g.tiles_x, tx = t - ty * g.tiles_x;
-  col = (tx << g.tw_log2) + (p & ((1 << g.tw_log2) - 1));
-  lr = (ty << (6 - g.tw_log2)) + (p >> g.tw_log2);
-  return col < fr.w && lr < fr.n_rows;
-}
-
 // accum[pixel] += staging[s][p] in sample order (stage_resolve) and the
 // Welford update of the sample luminance in stats[pixel] = {n, mean, M2, 0}.
 // LISTED: item i is lane i & 63 of tile tile_list[i >> 6]; pixels of unlisted
@@ -38,17 +28,16 @@ __global__ __launch_bounds__(kBlock) void stats_resolve(DevFrame fr, TileGrid g,
                                                         float* __restrict__ stats,
                                                         const int32_t* __restrict__ tile_list, int32_t nitems) {
   for (int32_t i = (int32_t)(blockIdx.x * kBlock + threadIdx.x); i < nitems; i += (int32_t)(gridDim.x * kBlock)) {
-    int32_t lr, col;
+    int32_t p = i;  // unlisted: item i is flat pixel i of the frame
+    size_t pix = LISTED ? 0 : frame_index(fr, i);
     if (LISTED) {
       const int32_t t = tile_list[i >> 6];
+      int32_t lr, col;
       if ((uint32_t)t >= (uint32_t)g.ntiles) continue;  // ids outside the grid are ignored
       if (!tile_pixel(fr, g, t, i & 63, col, lr)) continue;
-    } else {
-      lr = i / fr.w;
-      col = i - lr * fr.w;
+      p = lr * fr.w + col;
+      pix = frame_index(fr, lr, col);
     }
-    const int32_t p = lr * fr.w + col;
-    const size_t pix = (size_t)frame_row(fr, lr) * (size_t)fr.width + (size_t)(fr.x0 + col);
     float* ap = accum + 3 * pix;
     float4* stp = reinterpret_cast<float4*>(stats) + pix;
     float a0 = ap[0], a1 = ap[1], a2 = ap[2];
@@ -115,10 +104,7 @@ __global__ __launch_bounds__(kBlock) void tile_error(DevFrame fr, TileGrid g, co
   int32_t col, lr;
   const bool valid = tile_pixel(fr, g, t, lane, col, lr);
   float4 st = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-  if (valid) {
-    const size_t pix = (size_t)frame_row(fr, lr) * (size_t)fr.width + (size_t)(fr.x0 + col);
-    st = reinterpret_cast<const float4*>(stats)[pix];
-  }
+  if (valid) st = reinterpret_cast<const float4*>(stats)[frame_index(fr, lr, col)];
   const float n = st.x;
   const float e = n < 2.0f ? __builtin_inff() : sqrtf((st.z / (n - 1.0f)) / n) / (fabsf(st.y) + 0.01f);
   float v = valid ? e : 0.0f;

@@ -39,7 +39,7 @@ static inline FastDiv fast_div(uint32_t d) {
   while ((1ull << l) < d) ++l;
   return FastDiv{((1ull << (32 + l)) / d) + 1ull, 32u + l, d};
 }
-__device__ __forceinline__ uint32_t fdiv(uint32_t n, const FastDiv& f) { return (uint32_t)(((uint64_t)n * f.m) >> f.sh); }
+__host__ __device__ __forceinline__ uint32_t fdiv(uint32_t n, const FastDiv& f) { return (uint32_t)(((uint64_t)n * f.m) >> f.sh); }
 constexpr int kBlock = 256;
 
 // Register-budget stress build (libptmi_stress.so, tests/test_gpu_stress_build.py):
@@ -95,11 +95,23 @@ __device__ __forceinline__ int32_t leaf_index(int32_t ref) { return ref & 0x01ff
 __device__ __forceinline__ int32_t leaf_class(int32_t ref) { return (ref >> 25) & 7; }
 
 // Local row (0..n_rows-1) -> image row, or -1.
-__device__ __forceinline__ int32_t frame_row(const DevFrame& fr, int32_t lr) {
+__host__ __device__ __forceinline__ int32_t frame_row(const DevFrame& fr, int32_t lr) {
   int32_t band = lr / fr.band_rows;
   int32_t within = lr - band * fr.band_rows;
   int32_t row = fr.y0 + (band * fr.band_stride + fr.band_offset) * fr.band_rows + within;
   return (row < fr.y0 + fr.h) ? row : -1;
+}
+// The frame's pixel set is its n_rows local rows x w window columns, row-major.
+// (Local row, window column) -> the pixel's index in the image, and the same
+// for flat pixel p = lr * w + col of the set. The clears, the resolves and
+// tile_error address accum and stats through these; plan_check.cpp runs them.
+__host__ __device__ __forceinline__ size_t frame_index(const DevFrame& fr, int32_t lr, int32_t col) {
+  const int32_t px = fr.x0 + col, py = frame_row(fr, lr);
+  return (size_t)py * (size_t)fr.width + (size_t)px;
+}
+__host__ __device__ __forceinline__ size_t frame_index(const DevFrame& fr, int32_t p) {
+  const int32_t lr = p / fr.w;
+  return frame_index(fr, lr, p - lr * fr.w);
 }
 
 // ---------------------------------------------------------------- RNG

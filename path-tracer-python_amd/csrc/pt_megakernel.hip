@@ -271,7 +271,10 @@ __global__ __launch_bounds__(kMkBlock, stress_waves(STACK < 20 ? PTMI_MK_MIN_WAV
   bool live = false;
   // item -> tile origin (x, local row) and sample; persistent items are
   // unit-major: unit u = chunk u / csamp (tile chunk % ntiles, sample block
-  // chunk / ntiles), sample u % csamp of the block
+  // chunk / ntiles), sample u % csamp of the block. This persistent branch is
+  // the one decode that lives in its kernel: moved into a host/device function
+  // it compiled to other device code; plan_check.cpp's
+  // locate_host restates it and must change with it.
   struct Loc {
     int32_t x, row, s;  // tile origin (image x, local row), sample
   };
@@ -287,7 +290,7 @@ __global__ __launch_bounds__(kMkBlock, stress_waves(STACK < 20 ? PTMI_MK_MIN_WAV
         t = id;
       }
       const uint32_t ty = fdiv(t, wk.by_tiles_x);
-      return Loc{fr.x0 + ((int32_t)(t - ty * (uint32_t)wk.tiles_x) << wk.tw_log2), (int32_t)ty << (6 - wk.tw_log2),
+      return Loc{fr.x0 + tile_col0(wk.tw_log2, (int32_t)(t - ty * (uint32_t)wk.tiles_x)), tile_row0(wk.tw_log2, (int32_t)ty),
                  s_begin + (int32_t)(j - tq * (uint32_t)wk.nb)};
     }
     return Loc{sq_x, sq_y, s0 + (int32_t)(k >> 6)};
@@ -297,8 +300,8 @@ __global__ __launch_bounds__(kMkBlock, stress_waves(STACK < 20 ? PTMI_MK_MIN_WAV
     const Loc l = locate(k);
     s = l.s;
     const int twl = kPersist ? wk.tw_log2 : 3;
-    px = l.x + (p & ((1 << twl) - 1));
-    lr = l.row + (p >> twl);
+    px = l.x + lane_col(twl, p);
+    lr = l.row + lane_row(twl, p);
     py = (lr < fr.n_rows && px < fr.x0 + fr.w && s < s_begin + s_count) ? frame_row(fr, lr) : -1;
     if (STAGED) slot = (uint32_t)(s - s_begin) * (uint32_t)npix + (uint32_t)lr * (uint32_t)fr.w + (uint32_t)(px - fr.x0);
     return py >= 0;
@@ -791,10 +794,7 @@ __global__ __launch_bounds__(kMkBlock, stress_waves(STACK < 20 ? PTMI_MK_MIN_WAV
 __global__ __launch_bounds__(kBlock) void stage_resolve(DevFrame fr, const float* __restrict__ staging, int32_t npix,
                                                         int32_t batch, float* __restrict__ accum) {
   for (int32_t p = (int32_t)(blockIdx.x * kBlock + threadIdx.x); p < npix; p += (int32_t)(gridDim.x * kBlock)) {
-    int32_t lr = p / fr.w;
-    int32_t px = fr.x0 + (p - lr * fr.w);
-    int32_t py = frame_row(fr, lr);
-    float* ap = accum + 3 * ((size_t)py * (size_t)fr.width + (size_t)px);
+    float* ap = accum + 3 * frame_index(fr, p);
     float a0 = ap[0], a1 = ap[1], a2 = ap[2];
     const float* sp = staging + 3 * (size_t)p;
     for (int32_t s = 0; s < batch; ++s) {

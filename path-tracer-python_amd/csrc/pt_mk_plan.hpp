@@ -1,9 +1,11 @@
 // pt_mk_plan.hpp — the shape of a megakernel launch, decided on the host:
 // the frame's 64-pixel tiles, the staged workspace, the 32-bit item-id limit
-// and the work-unit plan of one staged batch. Host-only and pure: no HIP
-// runtime call and no kernel, so csrc/plan_check.cpp checks every plan on the
-// CPU. pt_megakernel.hip launches what mk_plan returns; pt_adaptive.hip and
-// pt_abi.hip read the same tile grid.
+// and the work-unit plan of one staged batch; and the tile grid's inverse,
+// the lane rule the kernels run (tile_col0, tile_row0, lane_col, lane_row,
+// tile_pixel: host and device). Pure: no HIP runtime call and no kernel, so
+// csrc/plan_check.cpp checks every plan, and the kernels' own lane rule, on
+// the CPU. pt_megakernel.hip launches what mk_plan returns; pt_adaptive.hip
+// and pt_abi.hip read the same tile grid.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -111,6 +113,28 @@ inline TileGrid tile_grid(const DevFrame& fr) {
   g.tiles_x = (fr.w + tw - 1) / tw;
   g.ntiles = g.tiles_x * ((fr.n_rows + th - 1) / th);  // <= pixels of the image: fits
   return g;
+}
+
+// The lane rule, stated here only: tile (tx, ty) of a grid of 1 << tw_log2
+// wide tiles starts at window column tx << tw_log2 and local row
+// ty << (6 - tw_log2), and lane p of a tile lies p & (tw - 1) columns and
+// p >> tw_log2 rows from there. Splitting a tile id into (tx, ty) is the
+// caller's (plain division in tile_pixel, FastDiv in the render kernels).
+// (One value per function: a caller keeps its own order of evaluation, and
+// with it the device code it had.)
+__host__ __device__ __forceinline__ int32_t tile_col0(int32_t tw_log2, int32_t tx) { return tx << tw_log2; }
+__host__ __device__ __forceinline__ int32_t tile_row0(int32_t tw_log2, int32_t ty) { return ty << (6 - tw_log2); }
+__host__ __device__ __forceinline__ int32_t lane_col(int32_t tw_log2, int32_t p) { return p & ((1 << tw_log2) - 1); }
+__host__ __device__ __forceinline__ int32_t lane_row(int32_t tw_log2, int32_t p) { return p >> tw_log2; }
+
+// Lane p of tile t -> the pixel's column in the window and its local row;
+// false outside the frame.
+__host__ __device__ __forceinline__ bool tile_pixel(const DevFrame& fr, const TileGrid& g, int32_t t, int32_t p,
+                                                    int32_t& col, int32_t& lr) {
+  const int32_t ty = t / g.tiles_x, tx = t - ty * g.tiles_x;
+  col = tile_col0(g.tw_log2, tx) + lane_col(g.tw_log2, p);
+  lr = tile_row0(g.tw_log2, ty) + lane_row(g.tw_log2, p);
+  return col < fr.w && lr < fr.n_rows;
 }
 
 // The staged workspace: staging[sample][pixel][3], then the shards' counter lines.

@@ -246,35 +246,9 @@ __device__ __forceinline__ void store_ray(const RayBuf& B, int32_t p, const Cont
   s_store(B.item + p, cn.item);
 }
 
-// Work items come in chunks of one 8x8 pixel square x csamp samples. Chunk c
-// is square c % nsq of sample block c / nsq (so early chunks cover every
-// square); item j of a chunk is pixel j % 64 of the square, sample j / 64 of
-// the block. A wave's 64 fresh rays are consecutive items, so they come
-// from one pixel square — the coherence the megakernel's waves get from
-// their 8x8 squares. Items outside the frame or past the batch are skipped.
-// it.p is the row-major pixel index (staging).
-struct Item {
-  int32_t srel, p, px, py;
-  bool valid;
-};
-// Tile-listed batches (the LISTED kernels; wf_plan with a tile list): a chunk
-// is one listed 64-pixel tile x csamp samples. Chunk c is virtual tile
-// v = c % n_list of sample block c / n_list (WfBufs::nsq holds n_list), the
-// frame tile is tiles[v], and item j of the chunk is that tile's lane j % 64
-// in the frame's tile grid (tile_grid, pt_mk_plan.hpp: row lane >> tw_log2,
-// column lane & (tw - 1) of the tile; WfBufs::sq_x holds its tiles per row) —
-// the pixels the tile id names in ptmi_tile_update, the listed megakernel and
-// the listed stats resolve. An id outside [0, ntiles) makes the chunk's 64
-// lanes invalid, like items outside the frame. The unlisted kernels carry no
+// The work items and their decode (Item, WfList, decode_item) are in
+// pt_wf_plan.hpp, beside the plan they invert. The unlisted kernels carry no
 // list: WfList<false> is empty and never a kernel argument.
-template <bool LISTED>
-struct WfList {};
-template <>
-struct WfList<true> {
-  const int32_t* tiles;  // device, n_list ids
-  int32_t ntiles;        // tiles of the frame's grid
-  int32_t tw_log2;       // tile width log2 (3: 8x8, 4: 16x4, 5: 32x2, 6: 64x1)
-};
 template <bool LISTED>
 __device__ __forceinline__ WfList<LISTED> wf_list() {
   return {};
@@ -282,41 +256,6 @@ __device__ __forceinline__ WfList<LISTED> wf_list() {
 template <bool LISTED>
 __device__ __forceinline__ WfList<LISTED> wf_list(const WfList<LISTED>& tl) {
   return tl;
-}
-
-__device__ __forceinline__ Item decode_item(const DevFrame& fr, const WfBufs& wb, const WfList<true>& tl, uint32_t k) {
-  Item it;
-  const uint32_t per = 64u * (uint32_t)wb.csamp;
-  const uint32_t c = fdiv(k, wb.by_per), j = k - c * per;
-  const uint32_t blk = fdiv(c, wb.by_nsq), v = c - blk * (uint32_t)wb.nsq;  // v < n_list
-  const int32_t id = s_load(tl.tiles + v);
-  const bool in_grid = (uint32_t)id < (uint32_t)tl.ntiles;
-  const uint32_t t = in_grid ? (uint32_t)id : 0u;  // (< 2^31: FastDiv's range)
-  const int32_t ty = (int32_t)fdiv(t, wb.by_sqx), tx = (int32_t)t - ty * wb.sq_x;
-  const uint32_t lane = j & 63u;
-  const int32_t lx = (tx << tl.tw_log2) + (int32_t)(lane & ((1u << tl.tw_log2) - 1u));
-  const int32_t lr = ty * (64 >> tl.tw_log2) + (int32_t)(lane >> tl.tw_log2);
-  it.srel = (int32_t)blk * wb.csamp + (int32_t)(j >> 6);
-  it.valid = in_grid && lx < fr.w && lr < fr.n_rows && it.srel < wb.batch;
-  it.p = lr * fr.w + lx;
-  it.px = fr.x0 + lx;
-  it.py = it.valid ? frame_row(fr, lr) : 0;
-  return it;
-}
-__device__ __forceinline__ Item decode_item(const DevFrame& fr, const WfBufs& wb, const WfList<false>&, uint32_t k) {
-  Item it;
-  // multiply-shift divisions (exact: items < 2^31, FastDiv)
-  const uint32_t per = 64u * (uint32_t)wb.csamp;
-  const uint32_t c = fdiv(k, wb.by_per), j = k - c * per;
-  const uint32_t blk = fdiv(c, wb.by_nsq), q = c - blk * (uint32_t)wb.nsq;
-  const int32_t qy = (int32_t)fdiv(q, wb.by_sqx), qx = (int32_t)q - qy * wb.sq_x;
-  const int32_t lx = qx * 8 + (int32_t)(j & 7u), lr = qy * 8 + (int32_t)((j >> 3) & 7u);
-  it.srel = (int32_t)blk * wb.csamp + (int32_t)(j >> 6);
-  it.valid = lx < fr.w && lr < fr.n_rows && it.srel < wb.batch;
-  it.p = lr * fr.w + lx;
-  it.px = fr.x0 + lx;
-  it.py = it.valid ? frame_row(fr, lr) : 0;
-  return it;
 }
 
 __device__ __forceinline__ uint32_t path_key(const DevFrame& fr, const WfBufs& wb, const Item& it) {

@@ -1,8 +1,9 @@
 // pt_wf_plan.hpp — the shape of a wavefront batch, decided on the host: the
 // workspace carved into every pipe's buffers, the batch's work items, the
-// grids and the id limit. Host-only and pure: no HIP runtime call and no
-// kernel, so csrc/plan_check.cpp checks every plan on the CPU.
-// pt_wavefront.hip launches what wf_plan returns.
+// grids and the id limit; and the plan's inverse, the work-item decode the
+// kernels run (decode_item: host and device). Pure: no HIP runtime call and no
+// kernel, so csrc/plan_check.cpp checks every plan, and the kernels' own
+// decode of it, on the CPU. pt_wavefront.hip launches what wf_plan returns.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -102,6 +103,72 @@ struct WfBufs {
   FastDiv by_per, by_nsq, by_sqx;  // item decode: / (64 * csamp), / nsq, / sq_x
 };
 
+// Work items come in chunks of one 8x8 pixel square x csamp samples. Chunk c
+// is square c % nsq of sample block c / nsq (so early chunks cover every
+// square); item j of a chunk is pixel j % 64 of the square, sample j / 64 of
+// the block. A wave's 64 fresh rays are consecutive items, so they come
+// from one pixel square — the coherence the megakernel's waves get from
+// their 8x8 squares. Items outside the frame or past the batch are skipped.
+// it.p is the row-major pixel index (staging).
+struct Item {
+  int32_t srel, p, px, py;
+  bool valid;
+};
+// Tile-listed batches (the LISTED kernels; wf_plan with a tile list): a chunk
+// is one listed 64-pixel tile x csamp samples. Chunk c is virtual tile
+// v = c % n_list of sample block c / n_list (WfBufs::nsq holds n_list), the
+// frame tile is tiles[v], and item j of the chunk is that tile's lane j % 64
+// in the frame's tile grid (the lane rule of pt_mk_plan.hpp;
+// WfBufs::sq_x holds its tiles per row) — the pixels the tile id names in
+// ptmi_tile_update, the listed megakernel and the listed stats resolve. An id
+// outside [0, ntiles) makes the chunk's 64 lanes invalid, like items outside
+// the frame.
+template <bool LISTED>
+struct WfList {};
+template <>
+struct WfList<true> {
+  const int32_t* tiles;  // device, n_list ids
+  int32_t ntiles;        // tiles of the frame's grid
+  int32_t tw_log2;       // tile width log2 (3: 8x8, 4: 16x4, 5: 32x2, 6: 64x1)
+};
+
+__host__ __device__ __forceinline__ Item decode_item(const DevFrame& fr, const WfBufs& wb, const WfList<true>& tl,
+                                                     uint32_t k) {
+  Item it;
+  const uint32_t per = 64u * (uint32_t)wb.csamp;
+  const uint32_t c = fdiv(k, wb.by_per), j = k - c * per;
+  const uint32_t blk = fdiv(c, wb.by_nsq), v = c - blk * (uint32_t)wb.nsq;  // v < n_list
+  const int32_t id = tl.tiles[v];
+  const bool in_grid = (uint32_t)id < (uint32_t)tl.ntiles;
+  const uint32_t t = in_grid ? (uint32_t)id : 0u;  // (< 2^31: FastDiv's range)
+  const int32_t ty = (int32_t)fdiv(t, wb.by_sqx), tx = (int32_t)t - ty * wb.sq_x;
+  const int32_t lane = (int32_t)(j & 63u);
+  const int32_t lx = tile_col0(tl.tw_log2, tx) + lane_col(tl.tw_log2, lane);
+  const int32_t lr = tile_row0(tl.tw_log2, ty) + lane_row(tl.tw_log2, lane);
+  it.srel = (int32_t)blk * wb.csamp + (int32_t)(j >> 6);
+  it.valid = in_grid && lx < fr.w && lr < fr.n_rows && it.srel < wb.batch;
+  it.p = lr * fr.w + lx;
+  it.px = fr.x0 + lx;
+  it.py = it.valid ? frame_row(fr, lr) : 0;
+  return it;
+}
+__host__ __device__ __forceinline__ Item decode_item(const DevFrame& fr, const WfBufs& wb, const WfList<false>&,
+                                                     uint32_t k) {
+  Item it;
+  // multiply-shift divisions (exact: items < 2^31, FastDiv)
+  const uint32_t per = 64u * (uint32_t)wb.csamp;
+  const uint32_t c = fdiv(k, wb.by_per), j = k - c * per;
+  const uint32_t blk = fdiv(c, wb.by_nsq), q = c - blk * (uint32_t)wb.nsq;
+  const int32_t qy = (int32_t)fdiv(q, wb.by_sqx), qx = (int32_t)q - qy * wb.sq_x;
+  const int32_t lx = qx * 8 + (int32_t)(j & 7u), lr = qy * 8 + (int32_t)((j >> 3) & 7u);
+  it.srel = (int32_t)blk * wb.csamp + (int32_t)(j >> 6);
+  it.valid = lx < fr.w && lr < fr.n_rows && it.srel < wb.batch;
+  it.p = lr * fr.w + lx;
+  it.px = fr.x0 + lx;
+  it.py = it.valid ? frame_row(fr, lr) : 0;
+  return it;
+}
+
 // Pipes: the rays are split into PTMI_WF_PIPES independent parts, each
 // driven through its own intersect/scatter loop on its own stream, so one
 // pipe's kernels fill the drain at the end of another's. They share the work
@@ -160,7 +227,7 @@ inline int64_t wf_max_batch_listed(int32_t n_list) {
 // listed 64-pixel tiles of the frame's tile grid (tile_grid, pt_mk_plan.hpp)
 // instead of the pixel set's 8x8 squares: chunk c is virtual tile c % n_list
 // of sample block c / n_list, and the kernels' LISTED decode reads the frame
-// tile from tile_list (WfList, pt_wavefront.hip). WfBufs::nsq / by_nsq then
+// tile from tile_list (WfList above). WfBufs::nsq / by_nsq then
 // hold n_list and sq_x / by_sqx the grid's tiles per row. Capacity, grids,
 // shard lengths and max_iters derive from the listed items (at most
 // min(npix, 64 * n_list) * nb paths are alive at once, so the ray buffers are

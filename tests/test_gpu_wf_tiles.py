@@ -242,6 +242,54 @@ def test_banded_window(integs):
     assert n == len(act) and eq(host(tiles['list'])[:n], act)
 
 
+BANDS = [(4, 2, 1), (2, 2, 1), (1, 2, 0)]
+
+
+@pytest.mark.parametrize('band', BANDS, ids=lambda b: '%dx%d' % (64 // b[0], b[0]))
+def test_banded_window_shapes(integs, band):
+    """The wavefront stats render on a 2-rank band frame, every tile shape a banded frame can have
+    (16 x 4, 32 x 2, 64 x 1): the 64 x 64 image, window x0 = 3, y0 = 2, 37 x 24
+    (12 owned rows, a ragged right edge), 3 samples on the whole frame, then 3
+    on a list of every second tile, an id outside the grid and the last (edge)
+    tile, then the tile update; bit for bit against the oracle."""
+    from ptmi import device
+    integ = integs
+    x0, y0, w, h = 3, 2, 37, 24
+    fr = make(64, (x0, y0, w, h), band)
+    th, tw = band[0], 64 // band[0]
+    tiles_x, tiles_y = -(-w // tw), 12 // th
+    nt = tiles_x * tiles_y
+    assert integ.tile_grid(fr) == (tw, th, tiles_x, tiles_y)
+    owned = device.frame_pixel_rows(fr)
+    assert len(owned) == 12
+    own = np.zeros((fr.height, fr.width), bool)
+    own[owned, x0:x0 + w] = True
+    cols, _ = ah.oracle_samples(SCENE, 64, 'wf', 0, 6, mask=own)
+    acc, stats = pattern(fr, 3, 0.5), pattern(fr, 4, 1.25)
+    integ.clear(fr, acc)
+    integ.clear_stats(fr, stats)
+    acc_ref, st_ref = host(acc).copy(), host(stats).copy()
+    integ.render_wf_stats(fr, acc, stats, 0, 3)
+    ah.accumulate(acc_ref, st_ref, cols[:3], own)
+    assert eq(host(acc), acc_ref) and eq(host(stats), st_ref)
+    ids = np.array(list(range(0, nt - 1, 2)) + [nt, nt - 1], np.int32)
+    local = ah.tile_mask(w, 12, tw, th, ids[ids < nt])
+    listed = np.zeros((fr.height, fr.width), bool)
+    lr, lc = np.nonzero(local)
+    listed[owned[lr], x0 + lc] = True
+    integ.reset_counters()
+    integ.render_wf_stats(fr, acc, stats, 3, 3, tiles=(dev(ids), len(ids)))
+    ah.accumulate(acc_ref, st_ref, cols[3:6], listed)
+    assert eq(host(acc), acc_ref) and eq(host(stats), st_ref)
+    assert set(np.unique(st_ref[own][:, 0])) == {3.0, 6.0}
+    assert integ.read_counters()['paths'] == int(listed.sum()) * 3
+    tiles = integ.new_tiles(fr)
+    n = integ.tile_update(fr, stats, 0.5, 6, 64, tiles)
+    new, E, act = ah.tile_update(np.ones(nt, np.int32), st_ref[owned][:, x0:x0 + w], tw, th, 0.5, 6, 64)
+    assert eq(host(tiles['err']), E) and eq(host(tiles['state']), new)
+    assert n == len(act) and eq(host(tiles['list'])[:n], act)
+
+
 # ---------------------------------------------------------------- 7: every rung
 def _rung(slots):
     """The wavefront's traversal kernel for max_leaf_depth + 1 stack slots (the coarse ladder)."""
