@@ -338,6 +338,17 @@ class _center:
         return self.origin + t * self.direction
 
 
+def _rigid_vec(R, v):
+    """``R * v``: ``R`` nine floats, row-major; every product rounded, then the sums of a row left to right."""
+    return vec3((R[0] * v.x + R[1] * v.y) + R[2] * v.z, (R[3] * v.x + R[4] * v.y) + R[5] * v.z,
+                (R[6] * v.x + R[7] * v.y) + R[8] * v.z)
+
+
+def rigid_point(R, c, c_t, p):
+    """``R * (p - c) + c_t`` in that order of operations (ptmi.rigid)."""
+    return _rigid_vec(R, p - c) + c_t
+
+
 class Sphere(hittable):
     @classmethod
     def stationary(cls, static_center, radius, mat):
@@ -374,6 +385,25 @@ class quad(hittable):
         self.bbox = aabb.from_aabbs(d1, d2)
         self.bbox._pad_to_minimums()
 
+    @classmethod
+    def transformed(cls, q, R, c, c_t):
+        """``q`` turned by ``R`` (nine floats, row-major) about ``c``, with ``c``
+        moved to ``c_t``: ``Q`` goes to ``R * (Q - c) + c_t``; ``u``, ``v``,
+        ``normal`` and ``w`` are each ``R *`` those of ``q`` (formed anew by the
+        constructor their last bits would differ, and ``length_squared``'s
+        ``x ** 2`` is not ``x * x``), so the normal is a unit vector only to
+        float64 rounding; ``D = normal.dot(Q)`` of the new values; the box by
+        the constructor's rule (ptmi.rigid)."""
+        t = cls.__new__(cls)
+        t.mat = q.mat
+        t.Q = Q = rigid_point(R, c, c_t, q.Q)
+        t.u, t.v, t.normal, t.w = (_rigid_vec(R, x) for x in (q.u, q.v, q.normal, q.w))
+        u, v = t.u, t.v
+        t.D = t.normal.dot(Q)
+        t.bbox = aabb.from_aabbs(aabb.from_points(Q, Q + u + v), aabb.from_points(Q + u, Q + v))
+        t.bbox._pad_to_minimums()
+        return t
+
 
 class triangle(hittable):
     def __init__(self, v0, v1, v2, mat):
@@ -396,6 +426,23 @@ class triangle(hittable):
         t.v0, t.v1, t.v2, t.mat = tri.v0 + offset, tri.v1 + offset, tri.v2 + offset, tri.mat
         t.edge1, t.edge2, t.normal = tri.edge1, tri.edge2, tri.normal
         v0, v1, v2 = t.v0, t.v1, t.v2
+        lo = point3(min(v0.x, v1.x, v2.x), min(v0.y, v1.y, v2.y), min(v0.z, v1.z, v2.z))
+        hi = point3(max(v0.x, v1.x, v2.x), max(v0.y, v1.y, v2.y), max(v0.z, v1.z, v2.z))
+        t.bbox = aabb.from_points(lo, hi)
+        t.bbox._pad_to_minimums()
+        return t
+
+    @classmethod
+    def transformed(cls, tri, R, c, c_t):
+        """``tri`` turned by ``R`` (nine floats, row-major) about ``c``, with
+        ``c`` moved to ``c_t``: the vertices each ``R * (p - c) + c_t``;
+        ``edge1``, ``edge2`` and ``normal`` each ``R *`` those of ``tri`` (the
+        normal is a unit vector only to float64 rounding); the box from the new
+        vertices (ptmi.rigid)."""
+        t = cls.__new__(cls)
+        t.mat = tri.mat
+        t.v0, t.v1, t.v2 = v0, v1, v2 = [rigid_point(R, c, c_t, p) for p in (tri.v0, tri.v1, tri.v2)]
+        t.edge1, t.edge2, t.normal = [_rigid_vec(R, x) for x in (tri.edge1, tri.edge2, tri.normal)]
         lo = point3(min(v0.x, v1.x, v2.x), min(v0.y, v1.y, v2.y), min(v0.z, v1.z, v2.z))
         hi = point3(max(v0.x, v1.x, v2.x), max(v0.y, v1.y, v2.y), max(v0.z, v1.z, v2.z))
         t.bbox = aabb.from_points(lo, hi)

@@ -15,8 +15,8 @@ import os
 import numpy as np
 import torch
 
-from . import (_lib, build as build_mod, bvh as bvh_mod, guide, material, motion, pose as pose_mod, post, temporal,
-               tree, update, validate, wf_tiles)
+from . import (_lib, build as build_mod, bvh as bvh_mod, guide, material, motion, pose as pose_mod, post,
+               rigid as rigid_mod, temporal, tree, update, validate, wf_tiles)
 from .scene_data import (BVH_KEYS, ByCode, ByStorage, DeviceLayout, KINDS, PRIM_SPHERE, STORAGE, SceneArrays,
                          camera_upload, counts_by_code, find_shell, node_slots, pack_device, shell_hint)
 
@@ -243,35 +243,78 @@ class DeviceScene:
         if self.posed is not None:
             raise _lib.PtmiError(f'the scene is posed at t = {self.posed!r}: unpose() first')
 
-    def set_tracks(self, spheres=None, quads=None, triangles=None, t_range=(0.0, 1.0)):
+    def set_tracks(self, spheres=None, quads=None, triangles=None, t_range=(0.0, 1.0), rigid=None):
         """Make the tracks of moving primitives resident (include/ptmi_pose.h,
         DESIGN.md §24). Each argument is ``(reference primitive indices, (n, 6 /
         9 / 12) f64 records)``: sphere {o, d}, quad {Q, d, normal}, triangle
         {v0, v1, v2, d} (``pose.track_records``); indices out of range or
         repeated and records of another shape or not finite are a ValueError.
+        ``rigid``: ``(bodies, rigid.body_records(bodies, prims))``, the rigid
+        bodies (include/ptmi_rigid.h) and per kind their
+        ``(indices, body index per entry, (n, 3 / 15 / 18) f64 rest records)``,
+        made resident next to the linear tracks; a primitive that is in a body
+        and has a linear track is a ValueError. With ``rigid=None`` nothing of
+        it is made and no call of it is ever issued.
         With them a *rest* edit list is uploaded: the mirror's own rows and
         build records of the tracked primitives, which ``unpose`` writes back.
         ``t_range``: the times ``pose`` will take. The shell hint of the posed
         scene is evaluated here, once: the scene is posed at both ends of the
         range, every tracked leaf gets the union of its two boxes (the box at
         any time between lies inside it: every step of the arithmetic is
-        monotone in t), and the layout's hint is kept if ``find_shell`` on
-        those boxes names the same leaf and that sphere is not tracked; else
-        the posed hint is 0. The scene is left unposed. Replaces earlier
-        tracks; no arguments clears them."""
+        monotone in t), a leaf of a body that turns gets ``rigid.swept_box``
+        instead (under rotation the two-ends argument is false), and the
+        layout's hint is kept if ``find_shell`` on those boxes names the same
+        leaf and that sphere is not tracked; else the posed hint is 0. The
+        scene is left unposed. Replaces earlier tracks and bodies; no
+        arguments clears them."""
         self._require_unposed()
         st = self._update_state()
         (t0, t1), _ = pose_mod.check_shutter(t_range, 1)
-        tracks = pose_mod.check_tracks(counts_by_code(self.layout), spheres, quads, triangles)
+        counts = counts_by_code(self.layout)
+        tracks = pose_mod.check_tracks(counts, spheres, quads, triangles)
         lists, keep = self._pack_edits(tracks, np.float64)
         indices = {t: idx for t, (idx, _) in tracks.items()}
+        bodies, rigid_lists, entries, rigid_keep = [], {}, {}, ()
+        if rigid is not None:
+            bodies, entries = rigid_mod.check_bodies(counts, *rigid)
+            for t, (idx, _, _) in entries.items():
+                if np.intersect1d(idx, indices.get(t, ())).size:
+                    raise ValueError('a primitive is in a rigid body and has a linear track')
+            recs, rigid_keep = self._pack_edits({t: (idx, rec) for t, (idx, _, rec) in entries.items()}, np.float64)
+            if entries:  # the body index of every entry, the kinds one after another as in ``recs``
+                body_ids = torch.from_numpy(np.concatenate([body for _, body, _ in entries.values()])).to(self.device)
+                rigid_keep += (body_ids,)
+                starts = np.cumsum([0] + [body.size for _, body, _ in entries.values()])
+                rigid_lists = {t: (prim, leaf, body_ids.data_ptr() + 4 * int(a), rec, n)
+                               for a, (t, (prim, leaf, rec, n)) in zip(starts, recs.items())}
+            indices = {t: np.union1d(indices.get(t, np.zeros(0, np.int64)), entries[t][0]) if t in entries
+                       else indices[t] for t in set(indices) | set(entries)}
         rest, rest_keep = self._pack_edits(update.current_edits(self.arrays, self.layout, st, indices))
+        # 'rigid_keep': the bodies' tensors, (device rows then leaves, rest records, body indices)
         self._tracks = {'lists': lists, 'rest': rest, 'keep': keep + rest_keep, 'indices': indices,
-                        't_range': (t0, t1), 'shell': 0}
-        self._tracks['shell'] = self._posed_shell(st, indices, t0, t1)
+                        't_range': (t0, t1), 'shell': 0, 'bodies': bodies, 'rigid': rigid_lists,
+                        'rigid_keep': rigid_keep, 'linear': bool(tracks) or not rigid_lists}
+        # per type code and body that turns, the reference indices of its primitives
+        self._tracks['turning'] = {(t, b): idx[body == b] for t, (idx, body, _) in entries.items()
+                                   for b in np.unique(body).tolist() if bodies[b].turn != 0.0}
+        self._tracks['shell'] = self._posed_shell(st, indices, t0, t1, self._tracks['turning'])
 
-    def _posed_shell(self, st, indices, t0, t1):
-        """The shell hint valid at every pose in [t0, t1] (set_tracks): the layout's, or 0."""
+    def set_t_range(self, t_range):
+        """Another ``t_range`` for the resident tracks and bodies: nothing is
+        uploaded, the posed shell hint is evaluated anew (as set_tracks does).
+        The per-frame step of an animation, whose shutter moves on while the
+        tracks stay. Needs set_tracks() first; the scene must be unposed."""
+        self._require_unposed()
+        tr = self._tracks
+        if tr is None:
+            raise _lib.PtmiError('set_t_range needs set_tracks() first')
+        tr['t_range'], _ = pose_mod.check_shutter(t_range, 1)
+        tr['shell'] = 0
+        tr['shell'] = self._posed_shell(self._update_state(), tr['indices'], *tr['t_range'], tr['turning'])
+
+    def _posed_shell(self, st, indices, t0, t1, turning=None):
+        """The shell hint valid at every pose in [t0, t1] (set_tracks): the layout's, or 0. ``turning``: per type
+        code and body that turns, the reference indices of its primitives."""
         lay, sa = self.layout, self.arrays
         if not lay.shell or not indices:
             return int(lay.shell)
@@ -288,6 +331,13 @@ class DeviceScene:
             leaves = st['leaf_of'][t][idx]
             bmin[leaves] = np.minimum(boxes[0][leaves, 0:3], boxes[1][leaves, 0:3])
             bmax[leaves] = np.maximum(boxes[0][leaves, 4:7], boxes[1][leaves, 4:7])
+        for (t, b), idx in (turning or {}).items():  # one swept_box call per body and kind, over all its leaves
+            leaves = st['leaf_of'][t][idx]
+            lo, hi = rigid_mod.swept_box(sa.bvh['bvh_bbox_min'][leaves], sa.bvh['bvh_bbox_max'][leaves],
+                                         self._tracks['bodies'][b], t0, t1)
+            # outwards to f32: the cast alone could round a bound inwards
+            bmin[leaves] = np.nextafter(lo.astype(np.float32), np.float32(-np.inf))
+            bmax[leaves] = np.nextafter(hi.astype(np.float32), np.float32(np.inf))
         swept = dataclasses.replace(sa, bvh=dict(sa.bvh, bvh_bbox_min=bmin, bvh_bbox_max=bmax))
         leaf = find_shell(swept, lay.max_leaf_depth)
         if leaf <= 0 or shell_hint(swept, st['slot_np'], lay.max_leaf_depth, self._pack[0]) != lay.shell:
@@ -297,16 +347,21 @@ class DeviceScene:
             return 0
         return int(lay.shell)
 
-    def pose_call(self, t, stream=None, flags=None):
-        """ptmi_pose_primitives on this scene's resident tracks at time ``t``:
-        asynchronous; the view's host fields and ``posed`` are not touched
-        (``pose`` does both). ``flags`` as for update_call."""
+    def _pose_time(self, t):
+        """The resident tracks and ``t`` as a float within their ``t_range``, or the pose calls' errors."""
         tr = self._tracks
         if tr is None:
             raise _lib.PtmiError('pose needs set_tracks() first')
         t = float(t)
         if not tr['t_range'][0] <= t <= tr['t_range'][1]:
             raise ValueError(f'pose: t = {t!r} is outside the tracks\' t_range {tr["t_range"]}')
+        return tr, t
+
+    def pose_call(self, t, stream=None, flags=None):
+        """ptmi_pose_primitives on this scene's resident tracks at time ``t``:
+        asynchronous; the view's host fields and ``posed`` are not touched
+        (``pose`` does both). ``flags`` as for update_call."""
+        tr, t = self._pose_time(t)
         st, arg = self._update_state(), _list_args(pose_mod.PoseList, tr['lists'])
         topo = self._topology(st, flags)
         with torch.cuda.device(self.device):
@@ -315,19 +370,43 @@ class DeviceScene:
                        'ptmi_pose_primitives')
         return t
 
+    def rigid_call(self, t, stream=None, flags=None):
+        """ptmi_pose_rigid on this scene's resident bodies at time ``t``, with the
+        host table ``rigid.body_table(bodies, t)``: asynchronous; the view's
+        host fields and ``posed`` are not touched (``pose`` does both).
+        ``flags`` as for update_call."""
+        tr, t = self._pose_time(t)
+        st, arg = self._update_state(), _list_args(rigid_mod.RigidList, tr['rigid'])
+        topo = self._topology(st, flags)
+        table = rigid_mod.body_table(tr['bodies'], t)
+        with torch.cuda.device(self.device):
+            _lib.check(rigid_mod.load().ptmi_pose_rigid(self.view, arg[0], arg[1], arg[2], table,
+                                                        len(tr['bodies']), C.byref(topo), st['root'].data_ptr(),
+                                                        _stream_ptr(stream, self.device)), 'ptmi_pose_rigid')
+        return t
+
     def pose(self, t, stream=None, flags=None):
-        """Put the tracked primitives where they are at time ``t`` and refit
-        (ptmi_pose_primitives): afterwards the device holds byte for byte what
-        ``update_primitives(*pose.posed_records(tracks, t))`` leaves. ``t``
-        outside set_tracks' ``t_range`` is a ValueError. One 24-byte readback
-        of the root box refreshes the view; the view's shell hint becomes the
-        posed one, and ``posed`` is ``t``. The mirror (``arrays``) and
-        ``layout`` keep describing the rest scene; ``unpose`` brings it back
-        (``pose(0.0)`` does not: Q + 0.0 * d turns a -0.0 into +0.0). No
+        """Put the tracked primitives where they are at time ``t`` and refit:
+        ptmi_pose_primitives if there are linear tracks (or no bodies), then
+        ptmi_pose_rigid if there are bodies. Afterwards the device holds byte
+        for byte what ``update_primitives`` leaves when given
+        ``pose.posed_records(tracks, t)`` and ``rigid.posed_records(bodies,
+        prims, t)``. With both kinds present the tree is refitted twice per
+        pose (about 40 us on the scenes measured: accepted).
+        ``t`` outside set_tracks' ``t_range`` is a ValueError. One 24-byte
+        readback of the root box refreshes the view; the view's shell hint
+        becomes the posed one, and ``posed`` is ``t``. The mirror (``arrays``)
+        and ``layout`` keep describing the rest scene; ``unpose`` brings it
+        back (``pose(0.0)`` does not: Q + 0.0 * d turns a -0.0 into +0.0). No
         render of this scene may be in flight on another stream. ``flags`` as
         for update_call."""
         s = _stream_or_current(stream, self.device)
-        self.posed = self.pose_call(t, s, flags)
+        tr, t = self._pose_time(t)
+        if tr['linear']:
+            self.pose_call(t, s, flags)
+        if tr['rigid']:
+            self.rigid_call(t, s, flags)
+        self.posed = t
         if self.view.num_bvh_nodes:
             with torch.cuda.device(self.device), torch.cuda.stream(s):
                 root = self._upd['root'].cpu().numpy()  # waits for the call on its stream
@@ -336,9 +415,10 @@ class DeviceScene:
 
     def unpose(self, stream=None):
         """The rest scene back on the device: ptmi_update_primitives on the
-        resident rest list restores every byte a pose changed; the view's root
-        box and shell hint are the layout's again and ``posed`` is None.
-        Asynchronous on ``stream``; nothing to do for an unposed scene."""
+        resident rest list restores every byte a pose changed, of linear tracks
+        and of bodies; the view's root box and shell hint are the layout's
+        again and ``posed`` is None. Asynchronous on ``stream``; nothing to do
+        for an unposed scene."""
         if self.posed is None:
             return
         self.update_call(self._tracks['rest'], stream)

@@ -67,8 +67,10 @@ t = 0, quirk Q22; its CPU renderers blur): with ``shutter=(t0, t1)`` every
 render call traces each slice of ``slice_spp`` samples with the moving
 primitives posed at that slice's shutter time (ptmi.pose) and
 leaves the device at the rest scene. Moving spheres are tracked by themselves;
-``set_motion`` gives quads and triangles a displacement. ``shutter=None``, the
-default, renders as before and makes no pose call.
+``set_motion`` gives quads and triangles a displacement, and ``set_bodies``
+makes groups of primitives rigid bodies that turn about an axis and move
+(ptmi.rigid). ``shutter=None``, the default, renders as before
+and makes no pose call.
 """
 from __future__ import annotations
 
@@ -80,7 +82,7 @@ import time
 import numpy as np
 import torch
 
-from . import _lib, build as build_mod, bvh as bvh_mod, core, device, pose as pose_mod, scene_compiler, tree as tree_mod
+from . import _lib, build as build_mod, bvh as bvh_mod, core, device, pose as pose_mod, rigid as rigid_mod, scene_compiler, tree as tree_mod
 from .scene_data import STORAGE, SceneArrays
 
 # kernels.py:746: the reference's switch between its front-to-back stack
@@ -157,6 +159,7 @@ class MI355XRenderer:
         self._motion = {'quads': {}, 'triangles': {}}
         self._motion_edits = 0
         self._tracks_key = None
+        self._bodies = []  # set_bodies' rigid bodies (ptmi.rigid)
         # launches per progress report: one launch renders many samples (path regeneration)
         self.samples_per_launch = int(samples_per_launch)
         device.require_gpu()
@@ -243,15 +246,56 @@ class MI355XRenderer:
                     self._motion[name][int(i)] = d.copy()
         self._motion_edits += 1
 
+    def _linearly_moving(self):
+        """{kind: the reference indices with a linear motion}: set_motion's entries and the moving spheres."""
+        tracks = pose_mod.tracks_of(self._prims, self._motion)
+        return {name: set(tracks[name]) for name in tracks}
+
+    def set_bodies(self, bodies):
+        """Make groups of primitives rigid bodies for ``shutter`` renders
+        (ptmi.rigid): ``bodies`` is a list of ``rigid.Body``, at
+        most ``rigid.MAX_BODIES``, and replaces all earlier ones; ``[]`` clears
+        them. A primitive that is in two bodies, that is both in a body and
+        linearly moving (a ``set_motion`` entry, or a sphere whose
+        ``center.direction`` is not zero), or that the scene does not have is a
+        ValueError. The resident scene, which is the rest pose, does not
+        change, and neither does an image without a shutter. Frame ``k`` of an
+        animation is ``shutter = (k * dt, k * dt + exposure)`` and a render:
+        ``shutter=(t, t)`` is the still pose at ``t``."""
+        bodies = list(bodies)
+        members = rigid_mod.members_of(bodies)
+        moving = self._linearly_moving()
+        for name, have in self._prims.items():
+            for i in members[name]:
+                if i >= len(have):
+                    raise ValueError(f'{name}: no primitive {i!r} (the scene has {len(have)})')
+                if i in moving[name]:
+                    raise ValueError(f'{name}[{i}] is in a body and moves linearly')
+        self._bodies = bodies
+        self._motion_edits += 1
+
     def _ensure_tracks(self):
-        """The resident tracks of the scene as it is now: made on the first use, remade when the scene, the
-        motion or the shutter has changed since (or the scene dropped them)."""
+        """The resident tracks of the scene as it is now: made on the first use, remade when the scene or the
+        motion has changed since (or the scene dropped them); when only the shutter has, the resident tracks get
+        the new range (DeviceScene.set_t_range: nothing is uploaded, which is what an animation's frame costs)."""
         shutter, self.slice_spp = pose_mod.check_shutter(self.shutter, self.slice_spp)
         key = (self.scene_revision, self._motion_edits, shutter)
-        if key != self._tracks_key or self.dscene._tracks is None:
+        if self._tracks_key is not None and key[:2] == self._tracks_key[:2] and self.dscene._tracks is not None:
+            if key != self._tracks_key:
+                torch.cuda.synchronize(self.dscene.device)  # set_t_range poses the scene: no render in flight
+                self.dscene.set_t_range(shutter)
+                self._tracks_key = key
+        else:
             torch.cuda.synchronize(self.dscene.device)  # set_tracks poses the scene: no render in flight
             tracks = pose_mod.tracks_of(self._prims, self._motion)
-            self.dscene.set_tracks(*pose_mod.track_records(tracks), t_range=shutter)
+            rigid = (self._bodies, rigid_mod.body_records(self._bodies, self._prims)) if self._bodies else None
+            if rigid is not None:  # a set_motion after set_bodies may have named a body's primitive
+                members = rigid_mod.members_of(self._bodies)
+                for name in tracks:
+                    both = sorted(set(tracks[name]) & set(members[name]))
+                    if both:
+                        raise ValueError(f'{name}[{both[0]}] is in a body and moves linearly')
+            self.dscene.set_tracks(*pose_mod.track_records(tracks), t_range=shutter, rigid=rigid)
             self._tracks_key = key
         return shutter
 
@@ -926,7 +970,8 @@ class MI355XRenderer:
                    'scene')
     # the shutter and the samples per pose: absent from a checkpoint written before there was a shutter, which is
     # one of an unblurred render
-    _SHUTTER_KEYS = {'shutter': np.zeros(0, np.float64), 'slice_spp': np.int64(0)}
+    # 'bodies': rigid.digest of set_bodies' bodies under a shutter; absent or '' means no bodies
+    _SHUTTER_KEYS = {'shutter': np.zeros(0, np.float64), 'slice_spp': np.int64(0), 'bodies': np.array('')}
 
     def _render_state(self):
         import hashlib
@@ -946,7 +991,8 @@ class MI355XRenderer:
         if self.shutter is None:
             return dict(self._SHUTTER_KEYS)
         shutter, slice_spp = pose_mod.check_shutter(self.shutter, self.slice_spp)
-        return {'shutter': np.array(shutter, np.float64), 'slice_spp': np.int64(slice_spp)}
+        return {'shutter': np.array(shutter, np.float64), 'slice_spp': np.int64(slice_spp),
+                'bodies': np.array(rigid_mod.digest(self._bodies) if self._bodies else '')}
 
     def save_checkpoint(self, path):
         """Write the accumulator and the next sample index (plain arrays, npz)
